@@ -5,9 +5,16 @@ A "step" = one pass of the hot path (encode_batch_dev then decode_batch_dev) ove
 synthetic pictures that are already resident in HBM.  Workload at every N: BASELINE.json config 2
 (UHD-1 3840x2160 4:2:2 10-bit, HQ_ConstQ, DD97, 4 levels, slices -u 1 -a 2, q 16, scalar 2);
 each rank/GPU owns its own batch of 128 distinct pictures (frames are independent: weak scaling, no collective on the data
-path; --streams 2 cuts the batch over two HIP streams: +1.4 % on one MI355X, per-kernel durations then overlap).  Prints ONE JSON line on rank 0:
+path; --streams 2 cuts the batch over two HIP streams: +1.4 % on one MI355X, per-kernel durations then overlap).  Prints ONE JSON line on rank 0.
 
-  value            encode+decode, device resident, K timed steps (barrier + synchronize on both sides)
+A plain run does what its headline needs and nothing else: it makes the pictures, warms up W steps, times exactly K steps,
+writes what the last step computed (--dump-outputs DIR) and prints the line:
+
+  value            encode+decode, device resident, K timed steps (barrier + synchronize on both sides); ms_per_step = their mean
+
+--full adds everything else, as the line carried it before the option existed (then `value` / `ms_per_step` are the median
+of three timed regions of K steps each, and every slot of the batch is checked before the line is printed):
+
   encode_only / decode_only   the two halves timed the same way, outside the timed region of `value`
   roofline         the dominant kernel (HIP events on each of its launches inside the timed region; every kernel in the warm-up steps) and the whole path
   e2e              pictures that start and end in pinned host memory, copies overlapped with kernels (PCIe bound)
@@ -17,7 +24,8 @@ path; --streams 2 cuts the batch over two HIP streams: +1.4 % on one MI355X, per
   other_configs    the other BASELINE configurations (cfg 1, 3, 4, 5-decode), 5 device-resident steps each, digest-checked
                    against tests/golden/reference_digests.json (cfg 5: against the oracle) -- beside `value`, never part of it
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--no-e2e] [--no-other-configs]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-e2e] [--no-other-configs] [--no-batch32]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 N > 1: one process per GPU over RCCL (backend nccl); every rank checks its own slots and the verdicts are AND-reduced
 before rank 0 prints.  --dist-backend gloo with VC2_BENCH_DEVICE_MAP=0,0 runs two ranks on ONE GPU (tests/test_multi_rank_gpu.py:
@@ -108,6 +116,35 @@ class ClockSampler:
 def picture_shard(n_pictures, rank, world):
     """Pictures are independent: picture k belongs to rank k mod world."""
     return list(range(rank, n_pictures, world))
+
+
+DUMP_SAMPLES = 1 << 22   # bytes of the coded slices and samples of the decoded pictures in the dumped samples: 16 MB each
+
+
+def dump_outputs(out_dir, torch, d_pay, stride, d_len, d_out, B, rb):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- every picture's coded slices (its
+    length and payload bytes) and every decoded picture -- as float arrays in DIR/<name>.npy, 32 MB in all.  In full: the
+    lengths and per-picture sums of the payload bytes and of the decoded samples (float64, exact); sampled: the bytes
+    and samples at DUMP_SAMPLES positions drawn by a fixed seed (float32; a payload position beyond its picture's length
+    reads -1).  Decoded samples are the raw pictures' 16-bit big-endian words."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    lens = d_len.cpu().numpy().astype(np.int64)
+    pay = d_pay.view(B, stride)
+    words = d_out.view(B, rb // 2, 2)
+    pay_sum = [int(pay[k, :int(lens[k])].sum(dtype=torch.int64)) for k in range(B)]
+    dec_sum = [256 * int(words[k, :, 0].sum(dtype=torch.int64)) + int(words[k, :, 1].sum(dtype=torch.int64)) for k in range(B)]
+    rng = np.random.default_rng(20260)
+    pos = np.sort(rng.integers(0, B * stride, size=DUMP_SAMPLES))
+    got = d_pay[torch.from_numpy(pos).to(d_pay.device)].cpu().numpy().astype(np.float32)
+    got[(pos % stride) >= lens[pos // stride]] = -1.0
+    wpos = np.sort(rng.integers(0, B * rb // 2, size=DUMP_SAMPLES))
+    hl = d_out.view(-1, 2)[torch.from_numpy(wpos).to(d_out.device)].cpu().numpy().astype(np.float32)
+    arrays = {"payload_lengths": lens.astype(np.float64), "payload_byte_sums": np.array(pay_sum, np.float64),
+              "payload_bytes_sampled": got, "decoded_sample_sums": np.array(dec_sum, np.float64),
+              "decoded_samples_sampled": hl[:, 0] * 256 + hl[:, 1]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def csrc_digest():
@@ -204,6 +241,12 @@ def main():
                          "115.9 / 117.5 / 121.7 / 117.2 / 118.4 / 119.9 Gpixel/s (the launch gaps, the ramps and the tails of sixteen "
                          "kernels per step are paid once per step, and every wavefront of the streaming kernels fills and drains its "
                          "ring once per launch; between the peaks the segment plan does not fill whole rounds of wavefront slots)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the per-kernel table and roofline, three timed regions, the halves, the "
+                         "32-picture step, the parity check of every slot, the CPU baseline, end to end, the other configurations "
+                         "(the options below thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float, 32 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes of the per-core CPU run (0: one per core)")
@@ -231,7 +274,7 @@ def main():
         return dry_run(args, rank, world)
 
     import numpy as np
-    from synth import synth
+    from synth import synth_fast
 
     t_start = time.perf_counter()
     B = args.batch
@@ -242,9 +285,9 @@ def main():
     # those frames with every plane rolled down by 64 rows per repetition -- distinct pictures, coded by the oracle like any other)
     G = min(B, 16)
     if rank == 0 or B <= 2:
-        frames = synth(W, H, CFMT, BITS, 1234, frames=G)
+        frames = synth_fast(W, H, CFMT, BITS, 1234, frames=G)
     else:
-        frames = synth(W, H, CFMT, BITS, 1234, frames=2) + synth(W, H, CFMT, BITS, 1234 + rank, frames=G - 2)
+        frames = synth_fast(W, H, CFMT, BITS, 1234, frames=2) + synth_fast(W, H, CFMT, BITS, 1234 + rank, frames=G - 2)
     if B > G:
         # (filled in place in ONE buffer: as a list of rolled copies joined at the end the same pictures cost a rank 90 s before it
         # touched the GPU, 70 of them in the kernel's page-fault handler -- VERDICT r5 item 8)
@@ -268,7 +311,7 @@ def main():
 
     # ---- CPU baseline first: nothing has touched the GPU yet, so forking worker processes is safe
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cores = os.cpu_count() or 1
         procs = args.cpu_procs or min(cores, B)
         cpu = cpu_reference(frames, rb, procs) + (cores, procs)
@@ -276,7 +319,7 @@ def main():
     # pool before it touches the GPU -- the parity verdict of an N-rank line is then against the oracle on every rank, not
     # only against the rank's own output in another slot.  (Not a baseline: nothing here is timed or reported.)
     oracle_slots = None
-    if world > 1 and not args.no_rank_oracle:
+    if args.full and world > 1 and not args.no_rank_oracle:
         import multiprocessing as mp
         ks = [k for k in (2, 3, 4, 5) if k < B]
         if ks:
@@ -319,7 +362,7 @@ def main():
     # THREE separately allocated output buffers, one per timed region: the physical placement of the
     # buffer the last inverse level writes moves that kernel by up to 15 %, and `value` should not be the
     # one draw a single allocation got -- it is the MEDIAN of the three regions, min and max beside it
-    d_outs = [torch.zeros(B * rb, dtype=torch.uint8, device=dev) for _ in range(3)]
+    d_outs = [torch.zeros(B * rb, dtype=torch.uint8, device=dev) for _ in range(3 if args.full else 1)]
     d_out = d_outs[0]
     torch.cuda.synchronize()
 
@@ -345,6 +388,51 @@ def main():
             fn()
         barrier()
         return time.perf_counter() - t0
+
+    def headline(dt, coded):
+        """the fields of a plain run's line (--full prints them first, then the rest)"""
+        return {
+            "metric": "Mpixels/s encode+decode, UHD-1 10-bit HQ_ConstQ",
+            "value": round(W * H * B * world * args.steps / dt / 1e6, 1),
+            "unit": "Mpixels/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int32",
+            "dtype_note": "the reference's arithmetic: every transform, quantiser and code value is computed as int32 in registers; "
+                          "the coefficient store between kernels holds int16 with an escape to int32 (exact for every input)",
+            "data": f"synthetic (SURVEY Appendix-B generator, seed 1234; {B} distinct pictures per GPU" + (f": {G} generated, the others those rolled by 64 rows per repetition" if B > G else "") +
+                    ("" if world == 1 else "; slots 2.. of rank r from seed 1234 + r") + ")",
+            "config": {"workload": "BASELINE cfg2: UHD-1 3840x2160 4:2:2 10-bit HQ_ConstQ DD97 depth 4, -u 1 -a 2 -q 16 -S 2",
+                       "pictures_per_gpu_per_step": B, "coded_bytes_per_picture": round(coded, 1), "streams": args.streams,
+                       "parallelism": f"frame-parallel x{world}, no collective"},
+        }
+
+    if not args.full:
+        # ---- a plain run: warm-up, exactly K timed steps, the outputs of the last one, the line
+        if args.streams > 1:
+            hip.set_streams(args.streams)
+        for _ in range(max(1, args.warmup)):
+            step()
+        hip.sync()
+        dt = timed(step, args.steps)
+        hip.sync()  # raises on any device-side error flag
+        if world > 1:
+            tmax = torch.tensor([dt], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)   # the slowest rank's time
+            dt = tmax.item()
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, torch, d_pay, stride, d_len, d_out, B, rb)
+            print(json.dumps(headline(dt, int(d_len.sum().item()) / B)))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the per-kernel table and the dominant kernel: ONE stream, the pictures of one launch (batch / streams), event pairs on
     # every launch, untimed.  (Paying for all ~30 event pairs of a step inside the timed region costs 4 % of it; and with
@@ -400,6 +488,8 @@ def main():
     dt = sorted(region_dt)[1]
     d_out = d_outs[region_dt.index(dt)]   # everything below (the other timings, the parity check) uses the median region's buffer
     same_out = all(torch.equal(d_outs[0], b) for b in d_outs[1:])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, d_pay, stride, d_len, d_out, B, rb)
     hip.profile_enable(False)
     hip.profile_only(None)
     prof = hip.profile()
@@ -567,24 +657,7 @@ def main():
                 traffic_note = f"committed profile {os.path.basename(f)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this bench), not collected by this run"
                 break
         out = {
-            "metric": "Mpixels/s encode+decode, UHD-1 10-bit HQ_ConstQ",
-            "value": round(total_px / dt / 1e6, 1),
-            "unit": "Mpixels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "dtype_note": "the reference's arithmetic: every transform, quantiser and code value is computed as int32 in registers; "
-                          "the coefficient store between kernels holds int16 with an escape to int32 (exact for every input)",
-            "data": f"synthetic (SURVEY Appendix-B generator, seed 1234; {B} distinct pictures per GPU" + (f": {G} generated, the others those rolled by 64 rows per repetition" if B > G else "") +
-                    ("" if world == 1 else "; slots 2.. of rank r from seed 1234 + r") + ")",
-            "config": {"workload": "BASELINE cfg2: UHD-1 3840x2160 4:2:2 10-bit HQ_ConstQ DD97 depth 4, -u 1 -a 2 -q 16 -S 2",
-                       "pictures_per_gpu_per_step": B, "coded_bytes_per_picture": round(coded, 1), "streams": args.streams,
-                       "parallelism": f"frame-parallel x{world}, no collective"},
+            **headline(dt, coded),
             "encode_only": {"value": round(total_px / dt_enc / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(dt_enc / args.steps * 1e3, 4)},
             "decode_only": {"value": round(total_px / dt_dec / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(dt_dec / args.steps * 1e3, 4)},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",

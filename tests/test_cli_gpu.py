@@ -293,7 +293,7 @@ def test_workers_on_distinct_devices(tools, oracle, tmp_path):
     """--devices 0,1: one worker, one library context and one pinned staging pool PER DEVICE (vc2hip_host_alloc on the
     worker's own device); the stream and the decoded file must be those of one device and of the oracle."""
     if _gpu_count() < 2:   # (asked inside the test: nothing touches torch or the GPU when the module is collected)
-        pytest.skip("needs two GPUs (the gpurun boxes have one): runs on the driver's multi-GPU node")
+        pytest.skip("needs two GPUs (the one-GPU machines have one): runs on the driver's multi-GPU node")
     w, h, frames = 512, 256, 9
     raw = synth(w, h, "422", 10, 67, frames=frames)
     p = make_params(w, h, "422", 10, "DD97", 4, 1, 2, q=16, scalar=2)

@@ -13,7 +13,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--no-e2e", "--no-other-configs"]
+COMMON = ["--steps", "3", "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline", "--no-e2e", "--no-other-configs"]
 
 
 def _free_port():

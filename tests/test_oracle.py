@@ -1,12 +1,11 @@
 """CPU tests that pin oracle/ (test infrastructure) to the reference:
   * the reference's own unit-test known answers (tests/Quantisation.cpp:6-36)
-  * the reference's quant_factor table (read from /root/reference when present)
+  * the reference's quant_factor table (tests/golden)
   * the reference's quantMatrix values (tests/golden)
   * the reference's own VLC.cpp compiled into oracle/_ref
   * internal invariants (q=0 lossless for all seven kernels, pack/unpack inverse)."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -30,13 +29,9 @@ def test_quant_index_limit_message(oracle):
     oracle.quant(12, 119)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/Library/src/Quantisation.cpp"),
-                    reason="reference checkout absent")
 def test_quant_factor_table_equals_reference(oracle):
-    src = open("/root/reference/src/Library/src/Quantisation.cpp").read()
-    body = src[src.index("lookup[120]"):src.index("if (q > (int)")]
-    body = "\n".join(l for l in body.splitlines() if not l.strip().startswith("//"))
-    table = [int(x, 16) for x in re.findall(r"0x[0-9A-Fa-f]+", body)]
+    # the reference's lookup[120] (Quantisation.cpp), recorded in tests/golden/quant_factor_table.json
+    table = [int(x, 16) for x in json.load(open(os.path.join(os.path.dirname(__file__), "golden", "quant_factor_table.json")))["quant_factor"]]
     assert len(table) == 120
     for q, want in enumerate(table):
         got = oracle.quant_factor(q) & 0xFFFFFFFF

@@ -38,7 +38,7 @@ def main(tag):
         shutil.copy(f'{d}/stats2/run_kernel_stats.csv', f'profiles/{tag}_rocprofv3_kernel_stats_two_streams.csv')
         shutil.copy(f'{d}/bench_under_rocprof_two_streams.json', f'profiles/{tag}_bench_under_rocprof_two_streams.json')
     with open(f'profiles/{tag}_pmc_instruction_mix.txt', 'w') as f:
-        f.write('# rocprofv3 --kernel-trace --pmc ... -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline (tools/prof_kernels.sh); '
+        f.write('# rocprofv3 --kernel-trace --pmc ... -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline (tools/prof_kernels.sh); '
                 'SQ_WAVE_CYCLES and the WAIT / ACTIVE counters are in 4-cycle units\n')
         f.write(subprocess.run([sys.executable, 'tools/pmc_mix.py', f'{d}/mix'], capture_output=True, text=True).stdout)
         f.write(subprocess.run([sys.executable, 'tools/pmc_mix2.py', f'{d}/mix2'], capture_output=True, text=True).stdout)
@@ -61,7 +61,7 @@ def main(tag):
     cfg = json.loads(open(f'{d}/bench_under_rocprof.json').read().strip().splitlines()[-1])["config"]   # the same command line as the PMC passes
     per_launch = cfg["pictures_per_gpu_per_step"] // max(1, cfg["streams"])
     res = {"_comment": "rocprofv3 PMC, two separate passes (--kernel-trace --pmc FETCH_SIZE ; --kernel-trace --pmc WRITE_SIZE) of "
-                       f"`python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-other-configs --no-batch32` ({cfg['pictures_per_gpu_per_step']} UHD cfg-2 pictures per step on {cfg['streams']} stream(s): {per_launch} per launch), averages "
+                       f"`python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-e2e --no-other-configs --no-batch32` ({cfg['pictures_per_gpu_per_step']} UHD cfg-2 pictures per step on {cfg['streams']} stream(s): {per_launch} per launch), averages "
                        "per launch. FETCH_SIZE/WRITE_SIZE are in KiB. hbm_bytes_per_launch applies the gfx950 correction of "
                        "MI355X_MICROARCH.md (FETCH_SIZE reports 1/2 of wide coalesced reads): 2*FETCH + WRITE -- an upper bound for "
                        "kernels whose reads are narrower than 16 bytes per lane. Names with several launches per step (dwt_level, "

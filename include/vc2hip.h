@@ -256,6 +256,35 @@ int vc2hip_decode_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t paylo
  * measurements -- the results never depend on it.  Extension, no counterpart in the reference. */
 int vc2hip_band_plane_bits(const vc2hip_ctx *ctx);
 
+/* The transform launches of the context's most recent call that ran a transform, one entry per launch, in launch order.
+ * Recorded on the host where the launch is issued; the planning passes of the decoder launch nothing and record nothing.
+ * Covers the context's own launches only.  A batch split over vc2hip_set_streams lanes leaves lane 0's sub-batch here
+ * (lane 0 is the context itself: `pictures` is its share); the other lanes and the pipelined picture calls run on child
+ * contexts and are not recorded.  Introspection for tests and measurements -- the results never depend on
+ * it.  Extension, no counterpart in the reference. */
+#define VC2HIP_DWT_TILE   0 /* generic LDS tile kernels (one level) */
+#define VC2HIP_DWT_FAST   1 /* fast tile kernels (one level) */
+#define VC2HIP_DWT_STREAM 2 /* streaming kernels (one level) */
+#define VC2HIP_DWT_PAIR   3 /* two-level kernels */
+#define VC2HIP_DWT_PLANE  4 /* whole planes in HBM: one entry per component, all levels */
+typedef struct {
+  int inverse;      /* 0 forward, 1 inverse */
+  int level;        /* finest level of the launch (0: the samples' level) */
+  int levels;       /* levels the launch covers: 1, 2 (PAIR), the transform depth (PLANE) */
+  int family;       /* VC2HIP_DWT_* */
+  int edge;         /* the launch reads (forward) or writes (inverse) raw sample words */
+  int store_bits;   /* coefficient store and level planes: 16 (with the escape planes) or 32 */
+  int segments;     /* STREAM / PAIR: segments per strip (the most of any component); else 0 */
+  int tail;         /* STREAM: the TAIL instantiation (a plane's pair count is not a multiple of the ring) */
+  int small_gather; /* FAST inverse: the element-wise gather for band blocks narrower than four coefficients */
+  int pictures;     /* pictures of the launch */
+  int band_planes;  /* inverse: the decoder's band planes the launch reads (0 = the slice records only, 16, 8: see
+                       vc2hip_band_plane_bits); PAIR: those of either of its levels */
+} vc2hip_dwt_launch;
+/* Copies up to `cap` entries into `out` (which may be null when cap is 0) and returns the number recorded (VC2HIP_EINVAL for a
+ * null context). */
+int vc2hip_dwt_launches(const vc2hip_ctx *ctx, vc2hip_dwt_launch *out, int cap);
+
 /* ---------------------------------------------------------------------------------------------
  * measurement: per-kernel HIP-event timing on the ctx stream (bench.py's roofline leg)
  * ------------------------------------------------------------------------------------------- */

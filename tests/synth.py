@@ -65,3 +65,27 @@ def noise_frame(w, h, cf, bits, seed, word_bytes=2, full_scale=False):
         else:
             out.append((v << (8 - bits)).astype(np.uint8).tobytes())
     return b''.join(out)
+
+
+def words_frame(w, h, cf, bits, seed, word_bytes, kind="noise"):
+    """A frame in words of 1 to 4 bytes (big-endian, MSB justified: what the ABI reads for any word size).  synth() and
+    synth_fast() make 1- and 2-byte words only, and their bytes are a digest contract, so wider words come from here.
+    kind: "noise" (uniform), "extremes" (every sample 0 or full scale) or "checker" (a full-scale checkerboard)."""
+    assert 1 <= word_bytes <= 4 and 1 <= bits <= 8 * word_bytes
+    rng = np.random.default_rng(seed)
+    cw = w if cf == '444' else w // 2
+    ch = h // 2 if cf == '420' else h
+    top = (1 << bits) - 1
+    out = []
+    for (pw, ph) in [(w, h), (cw, ch), (cw, ch)]:
+        if kind == "noise":
+            v = rng.integers(0, top + 1, size=(ph, pw), dtype=np.uint64)
+        elif kind == "extremes":
+            v = rng.integers(0, 2, size=(ph, pw), dtype=np.uint64) * np.uint64(top)
+        else:
+            yy, xx = np.mgrid[0:ph, 0:pw]
+            v = ((yy + xx) & 1).astype(np.uint64) * np.uint64(top)
+        v = v << np.uint64(8 * word_bytes - bits)
+        b = np.stack([(v >> np.uint64(8 * (word_bytes - 1 - k))) & np.uint64(0xFF) for k in range(word_bytes)], axis=-1)
+        out.append(b.astype(np.uint8).tobytes())
+    return b''.join(out)

@@ -49,7 +49,10 @@ def _check(variants, oracle, raw, w, h, cf, bits, kernel, depth, u, a, **kw):
 
 @pytest.mark.parametrize("kernel", list(KERNELS))
 def test_wide_all_kernels(variants, oracle, kernel):
-    # luma 1024 / chroma 512 wide: level 0 streams for both, level 1 only for luma, level 2 uses the tile kernels
+    # luma 1024 / chroma 512 wide (the launch record, vc2hip_dwt_launches): level 2 is 24 rows high, below a fast tile, so
+    # every variant keeps the int32 store and no two-level kernel runs; level 0 streams (edge form), level 1 goes through
+    # the fast tile kernels (the inverse with its small gather: chroma blocks 2 wide), level 2 through the generic tile
+    # kernels; the `tiles` variant takes the fast kernels at level 0 as well
     w, h, depth = 1024, 96, 3
     raw = noise_frame(w, h, "422", 10, seed=71)
     _check(variants, oracle, raw, w, h, "422", 10, kernel, depth, 1, 2, q=7, scalar=2)

@@ -26,6 +26,7 @@ void vc2_upload_tables_fast(const QuantTables &t, hipStream_t s);
 bool vc2_fast_level_applicable(LevelParams &p);
 int vc2_launch_forward_fast(Launcher &L, int kernel, bool first, const LevelParams &p, int n, bool store16, hipStream_t s);
 int vc2_launch_inverse_fast(Launcher &L, int kernel, bool final_level, const LevelParams &p, int n, bool store16, hipStream_t s);
+bool vc2_fast_small_gather(const LevelParams &p);
 void vc2_upload_tables_stream(const QuantTables &t, hipStream_t s);
 size_t vc2_stream_level_applicable(LevelParams &p, int kernel, bool edge, bool inverse, bool store16, int n_pictures);
 int vc2_launch_forward_stream(Launcher &L, int kernel, bool first, const LevelParams &p, int n, bool store16, size_t lds, hipStream_t s);
@@ -168,6 +169,8 @@ struct vc2hip_ctx {
   int stat_n = 0;                      // lengths copied
   int stat_n_total = 0;                // pictures of that batch (the escape count is over all of them)
   int last_plane_bits = 0;             // vc2hip_band_plane_bits: the most recent HQ decode call's band planes (0 none, 16, 8)
+  std::vector<vc2hip_dwt_launch> dwt_rec; // vc2hip_dwt_launches: the transform launches of the most recent call that ran one
+  bool dwt_rec_stale = true;              // set by every entry point: the next recorded launch starts a new record
   double stat_samples = 0;             // samples per picture of that batch
   int ld_batch = 1;         // pictures of the LD batch being encoded (fill_ld_enc sizes the scratch array with it)
   bool allow_heads = true;  // record heads for the levels below them (A/B and test switch VC2HIP_NO_HEADS)
@@ -444,6 +447,7 @@ static int join_lanes(vc2hip_ctx *c) {
 static int enter(vc2hip_ctx *c) {
   HIPCHK(c, hipSetDevice(c->device));
   if (!c->in_split) vc2_prof_break(c->L); // whatever the caller enqueued since is not part of the next kernel
+  c->dwt_rec_stale = true;
   return join_lanes(c);
 }
 #define ENTER(ctx) do { int rc_ = enter(ctx); if (rc_) return rc_; } while (0)
@@ -705,6 +709,22 @@ static void ll_layout(const Geom &g, int n, void *base, int elem_bytes, int32_t 
 }
 static void ll_layout(const Geom &g, int n, int32_t *base, LLPlanes &ll) { ll_layout(g, n, base, 4, nullptr, ll); }
 
+// vc2hip_dwt_launches: one entry per transform launch, on the host where it is issued
+static void record_dwt(vc2hip_ctx *c, bool inverse, int level, int levels, int family, bool edge, bool s16, int segments, int tail,
+                       bool small_gather, int n, int band_planes = 0) {
+  if (c->dwt_rec_stale) { c->dwt_rec.clear(); c->dwt_rec_stale = false; }
+  vc2hip_dwt_launch r;
+  r.inverse = inverse; r.level = level; r.levels = levels; r.family = family; r.edge = edge; r.store_bits = s16 ? 16 : 32;
+  r.segments = segments; r.tail = tail; r.small_gather = small_gather; r.pictures = n; r.band_planes = band_planes;
+  c->dwt_rec.push_back(r);
+}
+
+// the band planes an inverse level reads its bands from: 0 (the slice records), 16 or 8 (BandPlanes::bytes8)
+static int band_plane_bits(const LevelParams &p) {
+  for (int k = 0; k < 3; ++k) if (p.bp_base[k] >= 0) return p.bp8 ? 8 : 16;
+  return 0;
+}
+
 static void fill_level(LevelParams &p, const Geom &g, int level, int kernel, const int32_t *qm) {
   const int D = g.depth, Lv = D - level;
   p.band = 3 * (Lv - 1) + 1;
@@ -776,6 +796,7 @@ static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const vo
       if (lds) {
         int rc = vc2_launch_forward_pair(c->L, kernel, first, pp, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
+        record_dwt(c, false, level, 2, VC2HIP_DWT_PAIR, first, s16, pp.a.st_segmax, 0, false, n);
         ++level;
         continue;
       }
@@ -788,18 +809,21 @@ static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const vo
       if (lds) {
         int rc = vc2_launch_forward_stream(c->L, kernel, first, ps, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
+        record_dwt(c, false, level, 1, VC2HIP_DWT_STREAM, first, s16, ps.st_segmax, ps.st_tail, false, n);
         continue;
       }
     }
     if (!c->force_generic && vc2_fast_level_applicable(pf)) {
       int rc = vc2_launch_forward_fast(c->L, kernel, first, pf, n, s16, c->stream);
       if (rc) return set_err(c, rc, "invalid wavelet kernel");
+      record_dwt(c, false, level, 1, VC2HIP_DWT_FAST, first, s16, 0, 0, false, n);
       continue;
     }
     if (s16) return set_err(c, VC2HIP_EINVAL, "internal: 16-bit store without the fast level kernels");
     if (vc2_level_lds_bytes(kernel, p) > 160 * 1024) return set_err(c, VC2HIP_EINVAL, "slice too large for one LDS tile");
     int rc = vc2_launch_forward_level(c->L, kernel, first, p, n, c->stream);
     if (rc) return set_err(c, rc, "invalid wavelet kernel");
+    record_dwt(c, false, level, 1, VC2HIP_DWT_TILE, first, false, 0, 0, false, n);
   }
   return VC2HIP_OK;
 }
@@ -863,6 +887,8 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
       if (lds) {
         int rc = vc2_launch_inverse_pair(c->L, kernel, fin_a, pp, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
+        record_dwt(c, true, level - 1, 2, VC2HIP_DWT_PAIR, fin_a, s16, pp.a.st_segmax, 0, false, n,
+                   std::max(band_plane_bits(pp.a), band_plane_bits(pp.b)));
         --level;
         continue;
       }
@@ -876,6 +902,7 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
         if (stream_mask) { *stream_mask |= 1u << level; if (tail_mask && ps.st_tail) *tail_mask |= 1u << level; continue; }
         int rc = vc2_launch_inverse_stream(c->L, kernel, fin, ps, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
+        record_dwt(c, true, level, 1, VC2HIP_DWT_STREAM, fin, s16, ps.st_segmax, ps.st_tail, false, n, band_plane_bits(ps));
         continue;
       }
     }
@@ -884,12 +911,14 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
     if (!c->force_generic && vc2_fast_level_applicable(pf)) {
       int rc = vc2_launch_inverse_fast(c->L, kernel, fin, pf, n, s16, c->stream);
       if (rc) return set_err(c, rc, "invalid wavelet kernel");
+      record_dwt(c, true, level, 1, VC2HIP_DWT_FAST, fin, s16, 0, 0, vc2_fast_small_gather(pf), n, band_plane_bits(pf));
       continue;
     }
     if (s16) return set_err(c, VC2HIP_EINVAL, "internal: 16-bit store without the fast level kernels");
     if (vc2_level_lds_bytes(kernel, p) > 160 * 1024) return set_err(c, VC2HIP_EINVAL, "slice too large for one LDS tile");
     int rc = vc2_launch_inverse_level(c->L, kernel, fin, p, n, c->stream);
     if (rc) return set_err(c, rc, "invalid wavelet kernel");
+    record_dwt(c, true, level, 1, VC2HIP_DWT_TILE, fin, false, 0, 0, false, n, band_plane_bits(p));
   }
   return VC2HIP_OK;
 }
@@ -947,6 +976,7 @@ static int plane_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const 
                             cg.ph, cg.pw, n, c->stream);
     const int rc = vc2_launch_plane_transform(c->L, kernel, pl, ps, cg.ph, cg.pw, g.depth, false, n, c->stream);
     if (rc) return set_err(c, rc, "invalid wavelet kernel");
+    record_dwt(c, false, 0, g.depth, VC2HIP_DWT_PLANE, false, false, 0, 0, false, n);
     for (int p = 0; p < n; ++p)
       vc2_launch_plane_to_store(c->L, pl + (size_t)p * ps, cg.ph, cg.pw, g.depth, g.ys, g.xs,
                                 d_store + (size_t)p * g.ys * g.xs * g.slice_coefs, g.slice_coefs, cg.coef_off, c->stream);
@@ -978,6 +1008,7 @@ static int plane_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, const 
                                      cg.pw, g.depth, n, c->stream);
     const int rc = vc2_launch_plane_transform(c->L, kernel, pl, ps, cg.ph, cg.pw, g.depth, true, n, c->stream);
     if (rc) return set_err(c, rc, "invalid wavelet kernel");
+    record_dwt(c, true, 0, g.depth, VC2HIP_DWT_PLANE, false, false, 0, 0, false, n);
     vc2_launch_plane_emit(c->L, pl, ps, cg.pw, dst[k], ds[k], cg.h, cg.w, f->word_bytes, f->bit_depth, n, c->stream);
   }
   return VC2HIP_OK;
@@ -1870,6 +1901,13 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
 }
 
 extern "C" int vc2hip_band_plane_bits(const vc2hip_ctx *c) { return c ? c->last_plane_bits : 0; }
+
+extern "C" int vc2hip_dwt_launches(const vc2hip_ctx *c, vc2hip_dwt_launch *out, int cap) {
+  if (!c || cap < 0 || (cap && !out)) return VC2HIP_EINVAL;
+  const int n = (int)c->dwt_rec.size();
+  for (int i = 0; i < n && i < cap; ++i) out[i] = c->dwt_rec[i];
+  return n;
+}
 
 extern "C" int vc2hip_decode_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
                                        int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out) {

@@ -1064,6 +1064,16 @@ __global__ __launch_bounds__(NTK<K>) void k_inv_fast(const LevelParams p) {
   TILE_STAMP(5);
 }
 
+} // namespace
+
+// the inverse kernel's element-wise gather (launch_fast below; vc2hip_dwt_launches reports it)
+bool vc2_fast_small_gather(const LevelParams &p) {
+  for (int c = 0; c < 3; ++c) if (p.tiles_x[c] && p.fw[c] / 2 < 4) return true;
+  return false;
+}
+
+namespace {
+
 template <int K, bool EDGE, bool INV, class ST>
 void launch_fast(Launcher &L, const LevelParams &p, int n_pictures, hipStream_t s) {
   int gx = 0, gy = 0;
@@ -1082,8 +1092,7 @@ void launch_fast(Launcher &L, const LevelParams &p, int n_pictures, hipStream_t 
 #endif
   if constexpr (INV) {
     // element-wise gather when some component's band blocks are narrower than four coefficients
-    bool small = false;
-    for (int c = 0; c < 3; ++c) if (p.tiles_x[c] && p.fw[c] / 2 < 4) small = true;
+    const bool small = vc2_fast_small_gather(p);
     vc2_prof_begin(L, EDGE ? "idwt_level_final" : "idwt_level", s);
     if (small) {
       vc2_allow_lds((const void *)k_inv_fast<K, EDGE, true, ST>, 160 * 1024);

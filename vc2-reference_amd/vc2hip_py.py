@@ -40,6 +40,15 @@ class CodingParams(C.Structure):
                 ("compressed_bytes", C.c_int), ("prefix", C.c_int), ("scalar", C.c_int)]
 
 
+class DwtLaunch(C.Structure):
+    _fields_ = [("inverse", C.c_int), ("level", C.c_int), ("levels", C.c_int), ("family", C.c_int), ("edge", C.c_int),
+                ("store_bits", C.c_int), ("segments", C.c_int), ("tail", C.c_int), ("small_gather", C.c_int),
+                ("pictures", C.c_int), ("band_planes", C.c_int)]
+
+
+DWT_FAMILIES = ("tile", "fast", "stream", "pair", "plane")   # VC2HIP_DWT_TILE ... VC2HIP_DWT_PLANE
+
+
 class Vc2HipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(msg)
@@ -57,7 +66,7 @@ EXPORTS = [
     "vc2hip_decode_picture_ld", "vc2hip_encode_batch_dev", "vc2hip_decode_batch_dev",
     "vc2hip_profile_enable", "vc2hip_profile_only", "vc2hip_profile_count", "vc2hip_profile_get", "vc2hip_profile_reset",
     "vc2hip_host_alloc", "vc2hip_host_free", "vc2hip_encode_picture_begin", "vc2hip_encode_picture_end",
-    "vc2hip_decode_picture_begin", "vc2hip_decode_picture_end", "vc2hip_band_plane_bits",
+    "vc2hip_decode_picture_begin", "vc2hip_decode_picture_end", "vc2hip_band_plane_bits", "vc2hip_dwt_launches",
 ]
 
 
@@ -121,6 +130,7 @@ def load_library():
                                        C.POINTER(C.c_double)]
     lib.vc2hip_profile_reset.argtypes = [vp]
     lib.vc2hip_band_plane_bits.argtypes = [vp]
+    lib.vc2hip_dwt_launches.argtypes = [vp, C.POINTER(DwtLaunch), C.c_int]
     lib.vc2hip_host_alloc.argtypes = [C.c_size_t]
     lib.vc2hip_host_alloc.restype = vp
     lib.vc2hip_host_free.argtypes = [vp]
@@ -420,6 +430,20 @@ class Vc2Hip:
     def band_plane_bits(self):
         """0 / 16 / 8: the band planes of this context's most recent HQ decode call (vc2hip_band_plane_bits)"""
         return int(self.lib.vc2hip_band_plane_bits(self.h))
+
+    def dwt_launches(self):
+        """the transform launches of this context's most recent call that ran a transform (vc2hip_dwt_launches): one dict
+        per launch, family by name (DWT_FAMILIES)"""
+        n = self.lib.vc2hip_dwt_launches(self.h, None, 0)
+        self._chk(min(n, 0))
+        buf = (DwtLaunch * max(n, 1))()
+        n = self.lib.vc2hip_dwt_launches(self.h, buf, n)
+        out = []
+        for r in buf[:n]:
+            d = {name: getattr(r, name) for name, _ in DwtLaunch._fields_}
+            d["family"] = DWT_FAMILIES[d["family"]]
+            out.append(d)
+        return out
 
     def profile(self):
         out = {}

@@ -48,6 +48,7 @@ enum {
   VC2HIP_ECAP = -9,         /* caller's output buffer too small */
   VC2HIP_ESTREAM = -10,     /* truncated / malformed slice data */
   VC2HIP_ECODE32 = -11,     /* |quantised coefficient| > 65534: outside the reference's 32-bit VLC domain (VLC.h:27) */
+  VC2HIP_ESYNTAX = -12,     /* VC-2 stream syntax the stream calls refuse; vc2hip_last_error() names the failure and its byte offset */
   VC2HIP_EHIP = -100        /* HIP runtime failure (no device, out of memory, ...) */
 };
 
@@ -250,6 +251,49 @@ int vc2hip_encode_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
 int vc2hip_decode_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride,
                             const uint64_t *d_lens, int n, const vc2hip_picture_format *fmt,
                             const vc2hip_coding_params *cp, void *d_raw_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * VC-2 streams in device memory: the picture data units around the slots of the batch calls
+ *
+ *   raw pictures --encode_batch_dev--> slots + lens --stream_write_dev--> VC-2 stream bytes (device)
+ *   VC-2 stream bytes (device) --stream_read_dev--> slots + lens --decode_batch_dev--> raw pictures
+ *
+ * The stream calls only move bytes between the two layouts: they change no result of the batch calls.  They follow the
+ * batch calls' contract above (asynchronous on the ctx stream, 16-byte aligned slots and stride, no allocation, copy
+ * or host wait once the ctx has seen the geometry and batch size).  Errors the kernels find surface at vc2hip_sync:
+ * VC2HIP_ESYNTAX for a stream the reader refuses, VC2HIP_ECAP for a unit past `cap` or a payload past `payload_stride`.
+ * Extension, no counterpart in the reference (whose CLI tools build and walk streams on the host, DataUnit.cpp).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int major_version;             /* write: the stream's version, 1 - 3 (3 adds the two asymmetric-transform flags, DataUnit.cpp:249-252).  read: the
+                                    version before the stream's first sequence header (0: a picture before one is an error) */
+  uint32_t first_picture_number; /* write: picture k gets first_picture_number + k (mod 2^32), as utils::getPictureNumber */
+  uint32_t prev_parse_offset;    /* write: size of the data unit just before the first picture (the caller's sequence header) */
+  int end_of_sequence;           /* write: 1 appends the 13-byte end-of-sequence unit */
+} vc2hip_stream_params;
+
+/* Host only: picture number + transform parameters of one HQ / LD picture data unit (the bytes after its parse info),
+ * DataUnit.cpp:241-259 / :130-148.  HQ: slice prefix and scalar; LD (cp->mode == VC2HIP_LD): the slice-bytes fraction
+ * cp->compressed_bytes / (y_slices * x_slices) in lowest terms (utils::rationalise).  *len = the header's bytes (also on
+ * VC2HIP_ECAP, when they exceed cap). */
+int vc2hip_picture_header(const vc2hip_coding_params *cp, int major_version, uint32_t picture_number,
+                          uint8_t *out, size_t cap, size_t *len);
+/* Slots -> n picture data units (HQ or LD by cp->mode) at d_stream, then the end of sequence if asked for.  next / prev
+ * parse offsets are chained from sp->prev_parse_offset on.  *d_stream_len (device) = the bytes the units need, even past
+ * cap; nothing is written at or past cap (VC2HIP_ECAP at sync).  d_stream must be 16-byte aligned. */
+int vc2hip_stream_write_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
+                            const vc2hip_coding_params *cp, const vc2hip_stream_params *sp,
+                            uint8_t *d_stream, size_t cap, uint64_t *d_stream_len);
+/* The first n pictures of a stream (len bytes at d_stream, any alignment) -> slots + lens, plus each picture's number and the
+ * bytes consumed up to the end of the n-th picture (either may be NULL; a second call can resume at d_stream + consumed).
+ * Sequence headers give the major version; padding and auxiliary units are skipped; whole pictures and fragmented pictures
+ * (HQ and LD) are read.  Every picture's parameters must be those of cp.  VC2HIP_ESYNTAX at sync: a bad parse-info prefix,
+ * an unknown parse code, a unit past len, a picture whose next_parse_offset is 0, fewer than n pictures, parameters that
+ * differ from cp, a custom quantisation matrix, an asymmetric transform other than the identity, fragments out of order. */
+int vc2hip_stream_read_dev(vc2hip_ctx *ctx, const uint8_t *d_stream, size_t len, int n,
+                           const vc2hip_coding_params *cp, const vc2hip_stream_params *sp,
+                           void *d_payload, size_t payload_stride, uint64_t *d_lens,
+                           uint32_t *d_picture_numbers, uint64_t *d_consumed);
 
 /* Which form the band planes of the context's most recent HQ decode call had: 0 = none (the slice records only), 16 = 16-bit
  * elements, 8 = byte elements (see above: the adaptive choice, or the PLANES8 flags).  Introspection for tests and

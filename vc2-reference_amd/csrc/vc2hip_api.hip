@@ -128,14 +128,14 @@ struct Buf {
   size_t cap = 0;
 };
 enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS, B_LENS, B_PAYLOAD,
-       B_INDEX, B_PLANE, B_PLANE2, B_CBRB, B_CBRO, B_QM, B_COUNT };
+       B_INDEX, B_PLANE, B_PLANE2, B_CBRB, B_CBRO, B_QM, B_UNITS, B_SEGS, B_COUNT };
 
 struct vc2hip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   unsigned *d_err = nullptr;
-  unsigned *h_err = nullptr; // pinned
+  unsigned *h_err = nullptr; // pinned: the first VC2_ERRBLK_COPY bytes of the error block
   Buf buf[B_COUNT];
   Launcher L;
   std::string err;
@@ -218,6 +218,7 @@ static const char *code_text(int code) {
     case VC2HIP_ECAP: return "output buffer too small";
     case VC2HIP_ESTREAM: return "truncated or malformed slice data";
     case VC2HIP_ECODE32: return "quantised coefficient magnitude exceeds 65534 (outside the 32-bit exp-Golomb code domain)";
+    case VC2HIP_ESYNTAX: return "VC-2 stream syntax error";
     case VC2HIP_EHIP: return "HIP runtime error";
   }
   return "unknown error";
@@ -378,7 +379,7 @@ static int create_common(int device, hipStream_t stream, bool own, vc2hip_ctx **
   c->own_stream = own;
   if (hipMalloc((void **)&c->d_err, 256 + 4096) != hipSuccess || // error word, then the LD search tables
      
-      hipHostMalloc((void **)&c->h_err, sizeof(unsigned)) != hipSuccess ||
+      hipHostMalloc((void **)&c->h_err, VC2_ERRBLK_COPY) != hipSuccess ||
       hipMalloc((void **)&c->d_stat, 64) != hipSuccess || hipHostMalloc((void **)&c->h_stat, 64 * 8) != hipSuccess ||
       hipEventCreateWithFlags(&c->stat_ev, hipEventDisableTiming) != hipSuccess) { delete c; return VC2HIP_EHIP; }
   (void)hipMemsetAsync(c->d_stat, 0, 64, c->stream);
@@ -427,12 +428,27 @@ static int err_from_flags(vc2hip_ctx *c, unsigned f) {
     return set_err(c, VC2HIP_EHIP, "LD index search: a hand-over between workgroups timed out; nothing was written for the batch. "
                                    "The library now searches with one launch per slice diagonal: submit the batch again.");
   }
+  if (f & VC2_DEVERR_SYNTAX) {
+    static const char *why[VC2_SYN_COUNT] = {"?", "parse info prefix is not BBCD", "unknown parse code",
+                                             "data unit runs past the end of the stream", "next_parse_offset is 0",
+                                             "end of sequence before the pictures asked for",
+                                             "picture parameters differ from the coding parameters",
+                                             "custom quantisation matrix flag set", "asymmetric transform",
+                                             "picture before any sequence header and no major version given",
+                                             "fragment out of order"};
+    const unsigned w = *(const unsigned *)((const char *)c->h_err + VC2_ERRBLK_SYNTAX_WHY);
+    char b[256];
+    snprintf(b, sizeof b, "VC-2 stream syntax error at byte %llu: %s",
+             *(const unsigned long long *)((const char *)c->h_err + VC2_ERRBLK_SYNTAX_AT), why[w < VC2_SYN_COUNT ? w : 0]);
+    return set_err(c, VC2HIP_ESYNTAX, b);
+  }
   if (f & VC2_DEVERR_QINDEX) return set_err(c, VC2HIP_EQINDEX);
   if (f & VC2_DEVERR_SCALAR) return set_err(c, VC2HIP_ESCALAR);
   if (f & VC2_DEVERR_CBR_TOOBIG) return set_err(c, VC2HIP_ECBR_TOOBIG);
   if (f & VC2_DEVERR_CBR_LEN) return set_err(c, VC2HIP_ECBR_LEN);
   if (f & VC2_DEVERR_CODE32) return set_err(c, VC2HIP_ECODE32);
   if (f & VC2_DEVERR_LD_TOOBIG) return set_err(c, VC2HIP_ELD_TOOBIG);
+  if (f & VC2_DEVERR_CAP) return set_err(c, VC2HIP_ECAP);
   return set_err(c, VC2HIP_ESTREAM);
 }
 // make the context's stream wait for whatever its lanes still have in flight
@@ -530,7 +546,7 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
 extern "C" int vc2hip_sync(vc2hip_ctx *c) {
   if (!c) return VC2HIP_EINVAL;
   ENTER(c);
-  HIPCHK(c, hipMemcpyAsync(c->h_err, c->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_err, c->d_err, VC2_ERRBLK_COPY, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(unsigned), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->L.collect();
@@ -1901,6 +1917,112 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
 }
 
 extern "C" int vc2hip_band_plane_bits(const vc2hip_ctx *c) { return c ? c->last_plane_bits : 0; }
+
+// ------------------------------------------------------------------------------------------
+// VC-2 streams in device memory (vc2hip_stream.hip)
+// ------------------------------------------------------------------------------------------
+namespace {
+struct HeaderBits { // MSB-first writer of DataUnit.cpp's BitWriter
+  uint8_t *out;
+  size_t cap, pos = 0;
+  unsigned cache = 0;
+  int cached = 0;
+  void bit(unsigned b) {
+    cache = (cache << 1) | (b & 1);
+    if (++cached == 8) { if (pos < cap) out[pos] = (uint8_t)cache; ++pos; cache = 0; cached = 0; }
+  }
+  void uvlc(uint32_t v) { // interleaved exp-Golomb (VLC.cpp:21-52)
+    const unsigned long long x = (unsigned long long)v + 1;
+    int top = 63;
+    while (!(x >> top & 1)) --top;
+    for (int i = top - 1; i >= 0; --i) { bit(0); bit((unsigned)(x >> i) & 1); }
+    bit(1);
+  }
+  void align() { while (cached) bit(0); }
+};
+bool stream_cp_ok(const vc2hip_coding_params *cp) {
+  if (!cp || cp->kernel < 0 || cp->kernel > 6 || cp->depth < 0 || cp->y_slices < 1 || cp->x_slices < 1) return false;
+  if (cp->mode == VC2HIP_LD) return cp->compressed_bytes > 0;
+  return (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CBR) && cp->prefix >= 0 && cp->scalar >= 1;
+}
+// what the transform parameters carry after the slice counts: prefix, scalar (HQ) or the slice-bytes fraction in lowest
+// terms (LD: utils::rationalise(pictureBytes, slices), EncodeStream.cpp:263)
+void stream_ab(const vc2hip_coding_params *cp, uint32_t *a, uint32_t *b) {
+  if (cp->mode != VC2HIP_LD) { *a = (uint32_t)cp->prefix; *b = (uint32_t)cp->scalar; return; }
+  const int ns = cp->y_slices * cp->x_slices, g = gcd_i(cp->compressed_bytes, ns);
+  *a = (uint32_t)(cp->compressed_bytes / g);
+  *b = (uint32_t)(ns / g);
+}
+} // namespace
+
+extern "C" int vc2hip_picture_header(const vc2hip_coding_params *cp, int major_version, uint32_t picture_number, uint8_t *out,
+                                     size_t cap, size_t *len) {
+  if (!stream_cp_ok(cp) || major_version < 1 || !len || (cap && !out)) return VC2HIP_EINVAL;
+  uint32_t a, b;
+  stream_ab(cp, &a, &b);
+  HeaderBits w{out, cap};
+  for (int i = 24; i >= 0; i -= 8) for (int k = 7; k >= 0; --k) w.bit(picture_number >> (i + k)); // DataUnit.cpp: putBytes(4)
+  w.uvlc((uint32_t)cp->kernel);
+  w.uvlc((uint32_t)cp->depth);
+  if (major_version >= 3) { w.bit(0); w.bit(0); } // asym_transform_index_flag, asym_transform_flag
+  w.uvlc((uint32_t)cp->x_slices);
+  w.uvlc((uint32_t)cp->y_slices);
+  w.uvlc(a);
+  w.uvlc(b);
+  w.bit(0); // custom quantisation matrix
+  w.align();
+  *len = w.pos;
+  return w.pos > cap ? VC2HIP_ECAP : VC2HIP_OK;
+}
+
+extern "C" int vc2hip_stream_write_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
+                                       const vc2hip_coding_params *cp, const vc2hip_stream_params *sp, uint8_t *d_stream,
+                                       size_t cap, uint64_t *d_stream_len) {
+  if (!c || !d_payload || !d_lens || n < 1 || !cp || !sp || !d_stream || !d_stream_len) return set_err(c, VC2HIP_EINVAL);
+  if (((size_t)d_payload | payload_stride | (size_t)d_stream) & 15 || ((size_t)d_lens | (size_t)d_stream_len) & 7)
+    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  if (sp->major_version < 1) return set_err(c, VC2HIP_EINVAL, "major_version must be at least 1");
+  StreamWriteParams p;
+  memset(&p, 0, sizeof p);
+  size_t hl = 0;
+  if (vc2hip_picture_header(cp, sp->major_version, sp->first_picture_number, p.hdr, sizeof p.hdr, &hl))
+    return set_err(c, VC2HIP_EINVAL);
+  ENTER(c);
+  NEED(c, B_UNITS, (size_t)n * 8, p.unit_off);
+  p.payload = (const uint8_t *)d_payload; p.payload_stride = (long long)payload_stride;
+  p.lens = (const unsigned long long *)d_lens;
+  p.stream = d_stream; p.cap = cap; p.stream_len = (unsigned long long *)d_stream_len;
+  p.err = c->d_err;
+  p.n = n; p.hdr_len = (int)hl; p.code = cp->mode == VC2HIP_LD ? 0xC8 : 0xE8; p.eos = sp->end_of_sequence != 0;
+  p.first_picture_number = sp->first_picture_number; p.prev_parse_offset = sp->prev_parse_offset;
+  vc2_launch_stream_layout(c->L, p, c->stream);
+  vc2_launch_stream_copy(c->L, p, c->stream);
+  return VC2HIP_OK;
+}
+
+extern "C" int vc2hip_stream_read_dev(vc2hip_ctx *c, const uint8_t *d_stream, size_t len, int n, const vc2hip_coding_params *cp,
+                                      const vc2hip_stream_params *sp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
+                                      uint32_t *d_picture_numbers, uint64_t *d_consumed) {
+  if (!c || !d_stream || n < 1 || !cp || !sp || !d_payload || !d_lens) return set_err(c, VC2HIP_EINVAL);
+  if (((size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens | (size_t)d_consumed) & 7 || (size_t)d_picture_numbers & 3)
+    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  if (!stream_cp_ok(cp) || sp->major_version < 0 || payload_stride >= (1ull << 32)) return set_err(c, VC2HIP_EINVAL);
+  ENTER(c);
+  StreamReadParams p;
+  memset(&p, 0, sizeof p);
+  p.seg_cap = cp->y_slices * cp->x_slices + 1; // a picture unit is one segment, a fragment holds at least one slice
+  NEED(c, B_SEGS, (size_t)n * p.seg_cap * sizeof(StreamSeg), p.segs);
+  NEED(c, B_UNITS, (size_t)n * sizeof(uint2), p.meta);
+  p.stream = d_stream; p.len = len; p.n = n; p.major_version = sp->major_version;
+  p.kernel = cp->kernel; p.depth = cp->depth; p.ys = cp->y_slices; p.xs = cp->x_slices; p.ld = cp->mode == VC2HIP_LD;
+  stream_ab(cp, &p.a, &p.b);
+  p.payload = (uint8_t *)d_payload; p.payload_stride = (long long)payload_stride;
+  p.lens = (unsigned long long *)d_lens; p.picture_numbers = d_picture_numbers; p.consumed = (unsigned long long *)d_consumed;
+  p.err = c->d_err;
+  vc2_launch_stream_walk(c->L, p, c->stream);
+  vc2_launch_stream_gather(c->L, p, c->stream);
+  return VC2HIP_OK;
+}
 
 extern "C" int vc2hip_dwt_launches(const vc2hip_ctx *c, vc2hip_dwt_launch *out, int cap) {
   if (!c || cap < 0 || (cap && !out)) return VC2HIP_EINVAL;

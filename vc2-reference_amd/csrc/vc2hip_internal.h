@@ -29,6 +29,16 @@ enum : unsigned {
   VC2_DEVERR_STREAM = 1u << 5,     // slice data runs past the payload
   VC2_DEVERR_LD_TOOBIG = 1u << 6,
   VC2_DEVERR_HANDOFF = 1u << 7,    // LD index search: a row waited in vain for the row above (single-launch form)
+  VC2_DEVERR_CAP = 1u << 8,        // stream calls: a unit past the stream's cap, a payload past its slot
+  VC2_DEVERR_SYNTAX = 1u << 9,     // stream read: the walk stopped (reason and byte offset in the error block, VC2_ERRBLK_*)
+};
+// the error block (ctx->d_err, 256 bytes before the LD tables): word 0 the flags above, then
+#define VC2_ERRBLK_SYNTAX_AT 8      // uint64: byte offset of the stream syntax error
+#define VC2_ERRBLK_SYNTAX_WHY 16    // uint32: its reason (VC2_SYN_*)
+#define VC2_ERRBLK_COPY 32          // bytes vc2hip_sync copies back
+enum {
+  VC2_SYN_PREFIX = 1, VC2_SYN_CODE, VC2_SYN_PAST_END, VC2_SYN_NEXT_ZERO, VC2_SYN_FEWER, VC2_SYN_PARAMS, VC2_SYN_QUANT_MATRIX,
+  VC2_SYN_ASYMMETRIC, VC2_SYN_NO_VERSION, VC2_SYN_FRAGMENT, VC2_SYN_COUNT
 };
 
 struct CompGeom {
@@ -390,3 +400,40 @@ struct LdEncParams {
 };
 void vc2_launch_ld_quantise(Launcher &L, const LdEncParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_ld_pack(Launcher &L, const LdEncParams &p, int n_pictures, hipStream_t s);
+
+// VC-2 stream I/O (vc2hip_stream.hip)
+#define VC2_STREAM_HDR_MAX 48 // picture header bytes the write kernels carry (vc2hip_picture_header is far below it)
+struct StreamWriteParams {
+  const uint8_t *payload;           // slots
+  long long payload_stride;
+  const unsigned long long *lens;   // n payload lengths
+  unsigned long long *unit_off;     // workspace: n unit offsets
+  uint8_t *stream;
+  unsigned long long cap;
+  unsigned long long *stream_len;
+  unsigned *err;
+  int n, hdr_len, code, eos;
+  uint32_t first_picture_number, prev_parse_offset;
+  uint8_t hdr[VC2_STREAM_HDR_MAX]; // picture header of picture 0 (its number in bytes 0-3 is replaced per picture)
+};
+struct StreamSeg { unsigned long long src; uint32_t dst, len; }; // payload bytes [dst, dst + len) are stream bytes [src, ...)
+struct StreamReadParams {
+  const uint8_t *stream;
+  unsigned long long len;
+  int n, major_version;
+  int kernel, depth, ys, xs, ld;    // what every picture must carry
+  uint32_t a, b;                    // HQ: prefix, scalar.  LD: the slice-bytes fraction in lowest terms
+  StreamSeg *segs;                  // workspace: n * seg_cap
+  uint2 *meta;                      // workspace: per picture {segments, payload bytes}
+  int seg_cap;
+  uint8_t *payload;                 // slots
+  long long payload_stride;
+  unsigned long long *lens;
+  uint32_t *picture_numbers;        // may be null
+  unsigned long long *consumed;     // may be null
+  unsigned *err;
+};
+void vc2_launch_stream_layout(Launcher &L, const StreamWriteParams &p, hipStream_t s);
+void vc2_launch_stream_copy(Launcher &L, const StreamWriteParams &p, hipStream_t s);
+void vc2_launch_stream_walk(Launcher &L, const StreamReadParams &p, hipStream_t s);
+void vc2_launch_stream_gather(Launcher &L, const StreamReadParams &p, hipStream_t s);

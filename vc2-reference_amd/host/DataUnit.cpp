@@ -356,40 +356,25 @@ SequenceHeader readSequenceHeader(const unsigned char *p, std::size_t n, std::si
   return h;
 }
 
-static void putTransformParams(BitWriter &w, WaveletKernel kernel, int depth, bool v3_flags, int slices_x, int slices_y,
-                               unsigned a, unsigned b) {
-  w.putUnsignedVLC((unsigned)kernel);
-  w.putUnsignedVLC((unsigned)depth);
-  if (v3_flags) { w.putBoolean(false); w.putBoolean(false); } // asym_transform_index_flag, asym_transform_flag
-  w.putUnsignedVLC((unsigned)slices_x); w.putUnsignedVLC((unsigned)slices_y);
-  w.putUnsignedVLC(a); w.putUnsignedVLC(b);
-  w.putBoolean(false); // custom quantisation matrix
-  w.align();
+// the bit layout lives in the library (vc2hip_picture_header), which the device stream writer uses too
+std::vector<unsigned char> writePictureHeader(unsigned long picture_number, const vc2hip_coding_params &cp, int major_version) {
+  std::vector<unsigned char> out(64);
+  std::size_t len = 0;
+  const int rc = vc2hip_picture_header(&cp, major_version, (uint32_t)picture_number, out.data(), out.size(), &len);
+  if (rc != VC2HIP_OK) throw std::logic_error(std::string("picture header: ") + vc2hip_error_string(rc));
+  out.resize(len);
+  return out;
 }
 
 std::vector<unsigned char> writePictureHeaderHQ(unsigned long picture_number, WaveletKernel kernel, int depth,
                                                 int slices_x, int slices_y, int prefix, int scalar, int major_version) {
-  BitWriter w;
-  w.putBytes(4, picture_number);
-  putTransformParams(w, kernel, depth, major_version >= 3, slices_x, slices_y, (unsigned)prefix, (unsigned)scalar);
-  return w.bytes();
+  const vc2hip_coding_params cp = {(int)kernel, depth, slices_y, slices_x, VC2HIP_HQ_CONSTQ, 0, 0, prefix, scalar};
+  return writePictureHeader(picture_number, cp, major_version);
 }
 
-std::vector<unsigned char> writePictureHeaderLD(unsigned long picture_number, WaveletKernel kernel, int depth,
-                                                int slices_x, int slices_y, const utils::Rational &slice_bytes,
-                                                int major_version) {
-  BitWriter w;
-  w.putBytes(4, picture_number);
-  putTransformParams(w, kernel, depth, major_version >= 3, slices_x, slices_y, (unsigned)slice_bytes.numerator,
-                     (unsigned)slice_bytes.denominator);
-  return w.bytes();
-}
-
-std::vector<unsigned char> writeTransformParams(WaveletKernel kernel, int depth, bool v3_flags, int slices_x,
-                                                int slices_y, unsigned a, unsigned b) {
-  BitWriter w;
-  putTransformParams(w, kernel, depth, v3_flags, slices_x, slices_y, a, b);
-  return w.bytes();
+std::vector<unsigned char> writeTransformParams(const vc2hip_coding_params &cp) {
+  const std::vector<unsigned char> h = writePictureHeader(0, cp, 3);
+  return std::vector<unsigned char>(h.begin() + 4, h.end());
 }
 
 static void readParams(BitReader &r, bool low_delay, int major_version, PicturePreamble *pre) {

@@ -12,6 +12,7 @@
 #include "Picture.h"
 #include "Utils.h"
 #include "WaveletTransform.h"
+#include "vc2hip.h"
 
 enum DataUnitType { UNKNOWN_DATA_UNIT, SEQUENCE_HEADER, END_OF_SEQUENCE, AUXILIARY_DATA, PADDING_DATA,
                     HQ_PICTURE, LD_PICTURE, HQ_FRAGMENT, LD_FRAGMENT };
@@ -72,18 +73,15 @@ struct PicturePreamble {
   int depth, slices_x, slices_y, slice_prefix, slice_size_scalar;
   utils::Rational slice_bytes;
 };
-// picture header + transform parameters of an HQ / LD picture (DataUnit.cpp:241-259 / :130-148)
+// picture header + transform parameters of an HQ / LD picture (DataUnit.cpp:241-259 / :130-148), by vc2hip_picture_header:
+// HQ prefix and scalar, or LD's slice-bytes fraction from cp.compressed_bytes
+std::vector<unsigned char> writePictureHeader(unsigned long picture_number, const vc2hip_coding_params &cp, int major_version);
 std::vector<unsigned char> writePictureHeaderHQ(unsigned long picture_number, WaveletKernel kernel, int depth,
                                                 int slices_x, int slices_y, int prefix, int scalar,
                                                 int major_version);
-std::vector<unsigned char> writePictureHeaderLD(unsigned long picture_number, WaveletKernel kernel, int depth,
-                                                int slices_x, int slices_y, const utils::Rational &slice_bytes,
-                                                int major_version);
 // transform parameters alone, as the first fragment of a picture carries them: the two asymmetric-transform
-// flags are always present there (DataUnit.cpp:159-176 / :270-287).  a,b = prefix,scalar (HQ) or the
-// slice-bytes numerator,denominator (LD).
-std::vector<unsigned char> writeTransformParams(WaveletKernel kernel, int depth, bool v3_flags, int slices_x,
-                                                int slices_y, unsigned a, unsigned b);
+// flags are always present there (DataUnit.cpp:159-176 / :270-287)
+std::vector<unsigned char> writeTransformParams(const vc2hip_coding_params &cp);
 // DataUnit.cpp:1340-1410 without the picture number; returns bytes consumed
 std::size_t readTransformParams(const unsigned char *p, std::size_t n, bool low_delay, int major_version,
                                 PicturePreamble *pre);

@@ -260,7 +260,6 @@ int main(int argc, char *argv[]) {
       const std::chrono::steady_clock::time_point tCtx0 = std::chrono::steady_clock::now();
       GpuWorkers workers(devices, picBytes, vc2hip_max_payload_bytes(&pf, &cp) + 64);
       const double ctxSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tCtx0).count();
-      const utils::Rational ldRatio = utils::rationalise(pictureBytes, ySlices * xSlices);
       // ---- the ordered part of the writer
       std::mutex om;
       std::condition_variable ocv;
@@ -286,18 +285,14 @@ int main(int argc, char *argv[]) {
         bool payloadFollows = true;
         if (fragmented) {
           // DataUnit.cpp:156-232 / :267-342: parameters fragment + fragments of whole slices
-          const std::vector<unsigned char> params =
-              mode == LD ? writeTransformParams(kernel, waveletDepth, true, xSlices, ySlices, (unsigned)ldRatio.numerator, (unsigned)ldRatio.denominator)
-                         : writeTransformParams(kernel, waveletDepth, true, xSlices, ySlices, (unsigned)slicePrefix, (unsigned)sliceScalar);
+          const std::vector<unsigned char> params = writeTransformParams(cp);
           std::vector<std::size_t> sizes;
           if (mode == LD) for (std::size_t i = 0; i < ldSliceBytes.num_elements(); ++i) sizes.push_back((std::size_t)ldSliceBytes.data()[i]);
           else sizes = sliceSizesHQ(data, len, ySlices * xSlices, slicePrefix, sliceScalar);
           writeFragmentedPicture(head, mode == LD, picnum, params, data, sizes, xSlices, fragmentLength, &prev_parse_offset);
           payloadFollows = false;
         } else {
-          const std::vector<unsigned char> hdr =
-              mode == LD ? writePictureHeaderLD(picnum, kernel, waveletDepth, xSlices, ySlices, ldRatio, major_version)
-                         : writePictureHeaderHQ(picnum, kernel, waveletDepth, xSlices, ySlices, slicePrefix, sliceScalar, major_version);
+          const std::vector<unsigned char> hdr = writePictureHeader(picnum, cp, major_version);
           const unsigned long next = (unsigned long)(hdr.size() + len + 13);
           writeParseInfo(head, mode == LD ? LD_PICTURE : HQ_PICTURE, next, prev_parse_offset);
           prev_parse_offset = next;

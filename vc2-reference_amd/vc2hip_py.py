@@ -46,6 +46,11 @@ class DwtLaunch(C.Structure):
                 ("pictures", C.c_int), ("band_planes", C.c_int)]
 
 
+class StreamParams(C.Structure):
+    _fields_ = [("major_version", C.c_int), ("first_picture_number", C.c_uint32), ("prev_parse_offset", C.c_uint32),
+                ("end_of_sequence", C.c_int)]
+
+
 DWT_FAMILIES = ("tile", "fast", "stream", "pair", "plane")   # VC2HIP_DWT_TILE ... VC2HIP_DWT_PLANE
 
 
@@ -67,6 +72,7 @@ EXPORTS = [
     "vc2hip_profile_enable", "vc2hip_profile_only", "vc2hip_profile_count", "vc2hip_profile_get", "vc2hip_profile_reset",
     "vc2hip_host_alloc", "vc2hip_host_free", "vc2hip_encode_picture_begin", "vc2hip_encode_picture_end",
     "vc2hip_decode_picture_begin", "vc2hip_decode_picture_end", "vc2hip_band_plane_bits", "vc2hip_dwt_launches",
+    "vc2hip_picture_header", "vc2hip_stream_write_dev", "vc2hip_stream_read_dev",
 ]
 
 
@@ -123,6 +129,12 @@ def load_library():
                                             C.POINTER(CodingParams), vp, C.c_size_t, vp]
     lib.vc2hip_decode_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat),
                                             C.POINTER(CodingParams), vp]
+    lib.vc2hip_picture_header.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, u8p, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]
+    lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
+                                            vp, C.c_size_t, vp]
+    lib.vc2hip_stream_read_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
+                                           vp, C.c_size_t, vp, vp, vp]
     lib.vc2hip_profile_enable.argtypes = [vp, C.c_int]
     lib.vc2hip_profile_only.argtypes = [vp, C.c_char_p]
     lib.vc2hip_profile_count.argtypes = [vp]
@@ -157,6 +169,20 @@ def coding_params(lib, fmt, kernel, depth, u, a, mode="HQ_ConstQ", q=0, s=0, pre
     if not ys or not xs:
         raise ValueError("The given waveletDepth, hSlice, and vSlice parameters cannot encode this input.")
     return CodingParams(KERNELS[kernel], depth, ys, xs, MODES[mode], q, s, prefix, scalar)
+
+
+def stream_params(major_version=2, first_picture_number=0, prev_parse_offset=0, end_of_sequence=False):
+    return StreamParams(major_version, first_picture_number & 0xFFFFFFFF, prev_parse_offset, int(end_of_sequence))
+
+
+def picture_header(lib, cp, major_version, picture_number):
+    """vc2hip_picture_header (host only): the bytes after the parse info of an HQ / LD picture data unit"""
+    out = np.zeros(64, np.uint8)
+    n = C.c_size_t()
+    rc = lib.vc2hip_picture_header(C.byref(cp), major_version, picture_number & 0xFFFFFFFF, out, out.size, C.byref(n))
+    if rc != 0:
+        raise Vc2HipError(rc, lib.vc2hip_error_string(rc).decode())
+    return out[:n.value].tobytes()
 
 
 class Vc2Hip:
@@ -352,6 +378,18 @@ class Vc2Hip:
     def decode_batch_dev(self, d_payload, stride, d_lens, n, fmt, cp, d_raw_out):
         self._chk(self.lib.vc2hip_decode_batch_dev(self.h, d_payload, stride, d_lens, n, C.byref(fmt),
                                                    C.byref(cp), d_raw_out))
+
+    # ---- VC-2 streams in device memory (the slots + lengths of the batch calls <-> picture data units)
+    def picture_header(self, cp, major_version, picture_number):
+        return picture_header(self.lib, cp, major_version, picture_number)
+
+    def stream_write_dev(self, d_payload, stride, d_lens, n, cp, sp, d_stream, cap, d_stream_len):
+        self._chk(self.lib.vc2hip_stream_write_dev(self.h, d_payload, stride, d_lens, n, C.byref(cp), C.byref(sp), d_stream,
+                                                   cap, d_stream_len))
+
+    def stream_read_dev(self, d_stream, length, n, cp, sp, d_payload, stride, d_lens, d_picture_numbers=None, d_consumed=None):
+        self._chk(self.lib.vc2hip_stream_read_dev(self.h, d_stream, length, n, C.byref(cp), C.byref(sp), d_payload, stride,
+                                                  d_lens, d_picture_numbers, d_consumed))
 
     def encode_pictures_pipelined(self, raws, fmt, cp):
         """pictures in host memory through the pipelined calls (pinned staging, two in flight); returns the payloads"""

@@ -251,6 +251,27 @@ int vc2hip_encode_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
 int vc2hip_decode_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride,
                             const uint64_t *d_lens, int n, const vc2hip_picture_format *fmt,
                             const vc2hip_coding_params *cp, void *d_raw_out);
+/* Interlaced frames coded as field pictures (EncodeStream -i): each frame is two pictures of half its height, numbered
+ * per field, read from and written into the interleaved frames in place (no split or merge pass, no second raw buffer).
+ *   d_frames    n_frames frames packed as encode_batch_dev's pictures; frame_fmt is the FRAME's format
+ *   slots       2 * n_frames, in stream order: slot 2f = the first field of frame f, slot 2f + 1 = its second field
+ *   top_field_first  1: the first field is rows 0, 2, 4, ... of every plane; 0: rows 1, 3, 5, ...
+ *   cp          ONE FIELD picture: slices valid for the field heights (frame height / 2, frame chroma height / 2),
+ *               compressed_bytes the field's budget (EncodeStream passes -s / 2).  cp is used as given: no budget arithmetic.
+ * Otherwise the batch calls' contract above, word for word: all modes, wavelets, chroma formats, word_bytes 1 - 4 and
+ * chroma_bit_depth; 16-byte alignment; asynchronous on the ctx stream, errors at vc2hip_sync; vc2hip_set_streams splits by
+ * whole frames (lane i: frames [first, first + count), slots [2 first, 2 (first + count))), results identical.
+ * VC2HIP_EINVAL, nothing launched: an odd frame luma or chroma height (4:2:0: the frame height must be a multiple of 4).
+ * The slots and lengths equal encode_batch_dev's on the split fields; decode writes every byte of every frame.
+ * Extension, no counterpart in the reference (whose CLI tools split and merge the fields on the host). */
+int vc2hip_encode_fields_batch_dev(vc2hip_ctx *ctx, const void *d_frames, int n_frames,
+                                   const vc2hip_picture_format *frame_fmt, int top_field_first,
+                                   const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride,
+                                   uint64_t *d_lens);
+/* the inverse: 2 * n_frames field slots in stream order -> n_frames interleaved frames */
+int vc2hip_decode_fields_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride,
+                                   const uint64_t *d_lens, int n_frames, const vc2hip_picture_format *frame_fmt,
+                                   int top_field_first, const vc2hip_coding_params *cp, void *d_frames_out);
 
 /* ---------------------------------------------------------------------------------------------
  * VC-2 streams in device memory: the picture data units around the slots of the batch calls

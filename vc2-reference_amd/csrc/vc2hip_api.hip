@@ -37,9 +37,9 @@ int vc2_launch_inverse_pair(Launcher &L, int kernel, bool final_level, const Pai
 void vc2_upload_tables_pair(const QuantTables &t, hipStream_t s);
 int vc2_launch_plane_transform(Launcher &L, int kernel, int32_t *plane, long long plane_stride, int ph, int pw, int depth, bool inverse,
                                int n, hipStream_t s);
-void vc2_launch_plane_ingest(Launcher &L, const void *raw, long long raw_stride, int pic_h, int pic_w, int word_bytes, int bit_depth,
+void vc2_launch_plane_ingest(Launcher &L, const void *raw, const RawPlane &rl, int pic_h, int pic_w, int word_bytes, int bit_depth,
                              int32_t *plane, long long plane_stride, int ph, int pw, int n, hipStream_t s);
-void vc2_launch_plane_emit(Launcher &L, const int32_t *plane, long long plane_stride, int pw, void *raw, long long raw_stride, int pic_h,
+void vc2_launch_plane_emit(Launcher &L, const int32_t *plane, long long plane_stride, int pw, void *raw, const RawPlane &rl, int pic_h,
                            int pic_w, int word_bytes, int bit_depth, int n, hipStream_t s);
 void vc2_launch_ll_into_plane(Launcher &L, const int32_t *ll, long long ll_stride, int llh, int llw, int32_t *plane, long long plane_stride,
                               int pw, int depth, int n, hipStream_t s);
@@ -770,10 +770,10 @@ static void fill_level(LevelParams &p, const Geom &g, int level, int kernel, con
   for (int b = 0; b < 3 * D + 1; ++b) p.qmatrix[b] = qm ? qm[b] : 0;
 }
 
-// forward transform of n pictures: raw words (first level fused) or int32 LL_0 planes -> store
+// forward transform of n pictures: raw words (first level fused) or int32 LL_0 planes (src_l: stride only) -> store
 // s16: 16-bit store and level planes with their wide planes (only with the fast kernels: use_store16)
 static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const void *const src[3],
-                       const long long src_stride[3], bool src_raw, const vc2hip_picture_format *f,
+                       const RawPlane src_l[3], bool src_raw, const vc2hip_picture_format *f,
                        void *store, const LLPlanes &ll, bool s16 = false, int32_t *store_wide = nullptr) {
   auto level_params = [&](LevelParams &p, int level) {
     memset(&p, 0, sizeof p);
@@ -784,11 +784,13 @@ static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const vo
     p.ll_to_store = (level == g.depth - 1);
     const bool first = (level == 0) && src_raw;
     for (int k = 0; k < 3; ++k) {
-      if (level == 0) { p.plane[k] = (void *)src[k]; p.plane_stride[k] = src_stride[k]; }
+      if (level == 0) { p.plane[k] = (void *)src[k]; p.plane_stride[k] = src_l[k].stride; }
       else { p.plane[k] = ll.p[level][k]; p.plane_wide[k] = ll.w[level][k]; p.plane_stride[k] = ll.stride[level][k]; }
       p.ll[k] = ll.p[level + 1][k]; p.ll_wide[k] = ll.w[level + 1][k]; p.ll_stride[k] = ll.stride[level + 1][k];
     }
     if (first) {
+      for (int k = 0; k < 3; ++k) { p.raw_pitch[k] = src_l[k].pitch; p.field_step[k] = src_l[k].field_step; }
+      p.field_shift = src_l[0].field_shift;
       p.word_bytes = f->word_bytes;
       p.sample_shift = 8 * f->word_bytes - f->bit_depth;
       p.sample_offset = 1 << (f->bit_depth - 1);
@@ -850,7 +852,7 @@ static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const vo
 // the streaming kernel (the planning step of the band planes asks this before the slices are decoded).
 static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *store, const int32_t *qidx,
                        const int32_t *qm, bool dequant, bool ll_ready, const LLPlanes &ll, void *const dst[3],
-                       const long long dst_stride[3], bool dst_raw, const vc2hip_picture_format *f,
+                       const RawPlane *dst_l, bool dst_raw, const vc2hip_picture_format *f,
                        bool s16 = false, int32_t *store_wide = nullptr, const BandPlanes *bp = nullptr,
                        long long store_stride = 0, unsigned *stream_mask = nullptr, const HeadSplit *hs = nullptr, int head_level = 1 << 30,
                        unsigned *fast_mask = nullptr, unsigned *tail_mask = nullptr) {
@@ -870,11 +872,13 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
     p.ll_from_store = (level == g.depth - 1) && !ll_ready;
     const bool fin = (level == 0) && dst_raw;
     for (int k = 0; k < 3; ++k) {
-      if (level == 0) { p.plane[k] = dst ? dst[k] : nullptr; p.plane_stride[k] = dst_stride ? dst_stride[k] : 0; }
+      if (level == 0) { p.plane[k] = dst ? dst[k] : nullptr; p.plane_stride[k] = dst_l ? dst_l[k].stride : 0; }
       else { p.plane[k] = ll.p[level][k]; p.plane_wide[k] = ll.w[level][k]; p.plane_stride[k] = ll.stride[level][k]; }
       p.ll[k] = ll.p[level + 1][k]; p.ll_wide[k] = ll.w[level + 1][k]; p.ll_stride[k] = ll.stride[level + 1][k];
     }
     if (fin) {
+      for (int k = 0; k < 3; ++k) { p.raw_pitch[k] = dst_l[k].pitch; p.field_step[k] = dst_l[k].field_step; }
+      p.field_shift = dst_l[0].field_shift;
       p.word_bytes = f->word_bytes;
       p.sample_shift = 8 * f->word_bytes - f->bit_depth;
       p.sample_offset = 1 << (f->bit_depth - 1);
@@ -977,7 +981,7 @@ static size_t plane_elems(const Geom &g) {
   return e;
 }
 // raw pictures -> store (forward), general geometry
-static int plane_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const void *const src[3], const long long ss[3],
+static int plane_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const void *const src[3], const RawPlane ss[3],
                          const vc2hip_picture_format *f, int32_t *d_store) {
   int32_t *d_plane;
   NEED(c, B_PLANE, plane_elems(g) * n * 4, d_plane);
@@ -1002,7 +1006,7 @@ static int plane_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const 
 // store (quantised) -> raw pictures (inverse), general geometry
 // ll (LD pictures): the DC-predicted LL reconstruction of every component, which replaces the plane's LL band
 static int plane_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, const int32_t *d_store, const int32_t *d_q, const int32_t *qm,
-                         void *const dst[3], const long long ds[3], const vc2hip_picture_format *f, const LLPlanes *ll = nullptr) {
+                         void *const dst[3], const RawPlane ds[3], const vc2hip_picture_format *f, const LLPlanes *ll = nullptr) {
   int32_t *d_plane;
   int *d_qm;
   NEED(c, B_PLANE, plane_elems(g) * n * 4, d_plane);
@@ -1138,7 +1142,7 @@ extern "C" int vc2hip_dwt_forward(vc2hip_ctx *c, const int32_t *in, int h, int w
   ll_layout(g, 1, d_ll, ll);
   HIPCHK(c, hipMemcpyAsync(d_plane, padded.data(), pb, hipMemcpyHostToDevice, c->stream));
   const void *src[3] = {d_plane, nullptr, nullptr};
-  const long long ss[3] = {(long long)ph * pw, 0, 0};
+  const RawPlane ss[3] = {{(long long)ph * pw, 0, 0, 0}, {}, {}};
   rc = run_forward(c, g, kernel, 1, src, ss, false, nullptr, d_store, ll);
   if (rc) return rc;
   vc2_launch_store_to_plane(c->L, d_store, g.slice_coefs, 0, d_plane, ph, pw, depth, g.ys, g.xs, nullptr, nullptr, 0,
@@ -1166,7 +1170,7 @@ extern "C" int vc2hip_dwt_inverse(vc2hip_ctx *c, const int32_t *in, int ph, int 
   HIPCHK(c, hipMemcpyAsync(d_plane, in, pb, hipMemcpyHostToDevice, c->stream));
   vc2_launch_plane_to_store(c->L, d_plane, ph, pw, depth, g.ys, g.xs, d_store, g.slice_coefs, 0, c->stream);
   void *dst[3] = {d_plane, nullptr, nullptr};
-  const long long ds[3] = {(long long)ph * pw, 0, 0};
+  const RawPlane ds[3] = {{(long long)ph * pw, 0, 0, 0}, {}, {}};
   rc = run_inverse(c, g, kernel, 1, d_store, nullptr, nullptr, false, false, ll, dst, ds, false, nullptr);
   if (rc) return rc;
   std::vector<int32_t> full((size_t)ph * pw);
@@ -1578,15 +1582,27 @@ extern "C" int vc2hip_ld_pack(vc2hip_ctx *c, const int32_t *y, const int32_t *u,
 // ------------------------------------------------------------------------------------------
 // fused picture path
 // ------------------------------------------------------------------------------------------
-static void raw_planes(const vc2hip_picture_format *f, const void *base, const void *pl[3], long long stride[3]) {
+// The raw words of a batch of pictures of format f (vc2_raw_pic_offset).  fields == 1: progressive pictures, packed.
+// fields == 2: f is a FIELD's format, the pictures are the fields of packed interleaved frames (2 * f->height rows, and twice
+// the chroma rows), in stream order: the first field of a frame is its even rows when top_first, else its odd rows.
+static void raw_planes(const vc2hip_picture_format *f, const void *base, int fields, int top_first, const void *pl[3], RawPlane rl[3]) {
   int ch, cw;
   chroma_dims(f->height, f->width, f->chroma_format, &ch, &cw);
   const size_t ln = (size_t)f->height * f->width * f->word_bytes, cn = (size_t)ch * cw * f->word_bytes;
-  pl[0] = base;
-  pl[1] = (const uint8_t *)base + ln;
-  pl[2] = (const uint8_t *)base + ln + cn;
-  stride[0] = stride[1] = stride[2] = (long long)(ln + 2 * cn);
+  const int row[3] = {f->width * f->word_bytes, cw * f->word_bytes, cw * f->word_bytes};
+  const size_t at[3] = {0, fields * ln, fields * (ln + cn)};
+  for (int k = 0; k < 3; ++k) {
+    const bool second_first = fields == 2 && !top_first; // (the first field starts on the frame's row 1)
+    pl[k] = (const uint8_t *)base + at[k] + (second_first ? row[k] : 0);
+    rl[k].stride = (long long)fields * (ln + 2 * cn);
+    rl[k].pitch = fields * row[k];
+    rl[k].field_step = fields == 2 ? (top_first ? row[k] : -row[k]) : 0;
+    rl[k].field_shift = fields == 2;
+  }
 }
+
+static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int top_first, int n, const vc2hip_picture_format *f,
+                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens);
 
 extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
                                        const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride,
@@ -1608,6 +1624,12 @@ extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, 
                                        (uint8_t *)d_payload + (size_t)first * payload_stride, payload_stride, d_lens + first);
       });
   }
+  return encode_batch_common(c, d_raw, 1, 1, n, f, cp, d_payload, payload_stride, d_lens);
+}
+
+// n pictures of format f (raw_planes: progressive pictures, or the fields of interleaved frames) -> payload slots
+static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int top_first, int n, const vc2hip_picture_format *f,
+                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens) {
   if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD) return set_err(c, VC2HIP_EINVAL);
   if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
   if (cp->mode != VC2HIP_LD && (cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
@@ -1629,8 +1651,8 @@ extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, 
   NEED(c, B_QIDX, (size_t)n * ns * 4, d_q);
   LLPlanes ll;
   ll_layout(g, n, d_ll, s16 ? 2 : 4, d_llw, ll);
-  const void *src[3]; long long ss[3];
-  raw_planes(f, d_raw, src, ss);
+  const void *src[3]; RawPlane ss[3];
+  raw_planes(f, d_raw, fields, top_first, src, ss);
   if (needs_plane_path(c, g, cp->kernel)) { // (a slice beyond any LDS tile: HQ and LD alike -- the store is int32 then)
     if ((rc = plane_forward(c, g, cp->kernel, n, src, ss, f, d_store))) return rc;
   } else if ((rc = run_forward(c, g, cp->kernel, n, src, ss, true, f, d_store, ll, s16, d_storew))) return rc;
@@ -1689,7 +1711,8 @@ extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, 
 }
 
 static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
-                               const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out, bool ld) {
+                               const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out, bool ld,
+                               int fields = 1, int top_first = 1) {
   if (!c || !d_payload || n < 1 || !f || !cp || !d_raw_out) return set_err(c, VC2HIP_EINVAL);
   if (((size_t)d_raw_out | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
     return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
@@ -1702,8 +1725,8 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   int32_t qm[VC2_MAX_BANDS];
   if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
   const bool s16 = !ld && use_store16(c, g, cp->kernel);
-  const void *dstc[3]; long long ds[3];
-  raw_planes(f, d_raw_out, dstc, ds);
+  const void *dstc[3]; RawPlane ds[3];
+  raw_planes(f, d_raw_out, fields, top_first, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
   // Band planes (vc2hip_internal.h): the finest levels, as long as they go through the streaming inverse kernel, a
@@ -2048,6 +2071,73 @@ extern "C" int vc2hip_decode_batch_dev(vc2hip_ctx *c, const void *d_payload, siz
       });
   }
   return decode_batch_common(c, d_payload, payload_stride, d_lens, n, f, cp, d_raw_out, cp && cp->mode == VC2HIP_LD);
+}
+
+// Field pictures of interleaved frames (include/vc2hip.h): a field has the frame's format at half its height, so the
+// frame's luma and chroma heights must be even (as the host tools require of an interlaced frame: host/Frame.cpp).
+static int field_format(vc2hip_ctx *c, const vc2hip_picture_format *frame, vc2hip_picture_format *field) {
+  int ch, cw;
+  chroma_dims(frame->height, frame->width, frame->chroma_format, &ch, &cw);
+  if (frame->height < 2 || frame->height % 2 || ch % 2)
+    return set_err(c, VC2HIP_EINVAL, "field pictures need a frame whose luma and chroma heights are even (4:2:0: a multiple of 4)");
+  *field = *frame;
+  field->height = frame->height / 2;
+  return VC2HIP_OK;
+}
+
+extern "C" int vc2hip_encode_fields_batch_dev(vc2hip_ctx *c, const void *d_frames, int n_frames, const vc2hip_picture_format *frame_fmt,
+                                              int top_field_first, const vc2hip_coding_params *cp, void *d_payload,
+                                              size_t payload_stride, uint64_t *d_lens) {
+  if (!c || !d_frames || n_frames < 1 || !frame_fmt || !cp || !d_payload || !d_lens)
+    return set_err(c, VC2HIP_EINVAL, "encode_fields_batch_dev: a null argument or fewer than one frame");
+  if (((size_t)d_frames | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
+    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  vc2hip_picture_format ff;
+  int rc = field_format(c, frame_fmt, &ff);
+  if (rc) return rc;
+  if (c->lanes.size() > 1 && n_frames > 1 && !c->in_split) { // whole frames per lane: frames [first, first + count), slots twice that
+    const size_t fb = vc2hip_raw_picture_bytes(frame_fmt);
+    const uint8_t *raw8 = (const uint8_t *)d_frames, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
+    return split_batch(c, n_frames,
+      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
+        u.r[0] = {raw8 + (size_t)first * fb, raw8 + (size_t)(first + count) * fb}; u.r[1] = {nullptr, nullptr};
+        u.w[0] = {pay8 + (size_t)2 * first * payload_stride, pay8 + (size_t)2 * (first + count) * payload_stride};
+        u.w[1] = {len8 + (size_t)2 * first * 8, len8 + (size_t)2 * (first + count) * 8};
+      },
+      [&](vc2hip_ctx *l, int first, int count) {
+        return vc2hip_encode_fields_batch_dev(l, raw8 + (size_t)first * fb, count, frame_fmt, top_field_first, cp,
+                                              (uint8_t *)d_payload + (size_t)2 * first * payload_stride, payload_stride,
+                                              d_lens + 2 * first);
+      });
+  }
+  return encode_batch_common(c, d_frames, 2, top_field_first != 0, 2 * n_frames, &ff, cp, d_payload, payload_stride, d_lens);
+}
+
+extern "C" int vc2hip_decode_fields_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
+                                              int n_frames, const vc2hip_picture_format *frame_fmt, int top_field_first,
+                                              const vc2hip_coding_params *cp, void *d_frames_out) {
+  if (!c || !d_payload || n_frames < 1 || !frame_fmt || !cp || !d_frames_out)
+    return set_err(c, VC2HIP_EINVAL, "decode_fields_batch_dev: a null argument or fewer than one frame");
+  vc2hip_picture_format ff;
+  int rc = field_format(c, frame_fmt, &ff);
+  if (rc) return rc;
+  if (c->lanes.size() > 1 && n_frames > 1 && !c->in_split) {
+    const size_t fb = vc2hip_raw_picture_bytes(frame_fmt);
+    const uint8_t *out8 = (const uint8_t *)d_frames_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
+    return split_batch(c, n_frames,
+      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
+        u.r[0] = {pay8 + (size_t)2 * first * payload_stride, pay8 + (size_t)2 * (first + count) * payload_stride};
+        u.r[1] = {len8 ? len8 + (size_t)2 * first * 8 : nullptr, len8 ? len8 + (size_t)2 * (first + count) * 8 : nullptr};
+        u.w[0] = {out8 + (size_t)first * fb, out8 + (size_t)(first + count) * fb}; u.w[1] = {nullptr, nullptr};
+      },
+      [&](vc2hip_ctx *l, int first, int count) {
+        return vc2hip_decode_fields_batch_dev(l, pay8 + (size_t)2 * first * payload_stride, payload_stride,
+                                              d_lens ? d_lens + 2 * first : nullptr, count, frame_fmt, top_field_first, cp,
+                                              (uint8_t *)d_frames_out + (size_t)first * fb);
+      });
+  }
+  return decode_batch_common(c, d_payload, payload_stride, d_lens, 2 * n_frames, &ff, cp, d_frames_out, cp->mode == VC2HIP_LD, 2,
+                             top_field_first != 0);
 }
 
 extern "C" int vc2hip_encode_picture_hq(vc2hip_ctx *c, const void *raw, const vc2hip_picture_format *f,

@@ -135,8 +135,8 @@ __global__ __launch_bounds__(256) void k_fwd_level(const LevelParams p) {
     if (gy >= 0 && gy < in_h && gx >= 0 && gx < in_w) {
       if constexpr (FIRST) {
         const int sy = min(gy, p.pic_h[comp] - 1), sx = min(gx, p.pic_w[comp] - 1);
-        const uint8_t *src = (const uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] +
-                             ((size_t)sy * p.pic_w[comp] + sx) * p.word_bytes;
+        const uint8_t *src = (const uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +
+                             (size_t)sy * p.raw_pitch[comp] + (size_t)sx * p.word_bytes;
         unsigned u;
         if (p.word_bytes == 2) {
           const unsigned short h = *(const unsigned short *)src;
@@ -259,8 +259,8 @@ __global__ __launch_bounds__(256) void k_inv_level(const LevelParams p) {
     if constexpr (FINAL) {
       v = min(max(v, p.clip_lo), p.clip_hi);
       const unsigned u = (unsigned)(v + p.sample_offset) << p.sample_shift;
-      uint8_t *dst = (uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] +
-                     ((size_t)gy * lim_w + gx) * p.word_bytes;
+      uint8_t *dst = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +
+                     (size_t)gy * p.raw_pitch[comp] + (size_t)gx * p.word_bytes;
       if (p.word_bytes == 2) {
         *(unsigned short *)dst = (unsigned short)(((u & 0xFF) << 8) | ((u >> 8) & 0xFF));
       } else {

@@ -398,6 +398,7 @@ __global__ __launch_bounds__(NTK<K>) void k_fwd_fast(const LevelParams p) {
   // latency per tile instead of one per item.
   {
     const int pic_h = p.pic_h[comp], pic_w = p.pic_w[comp];
+    // (16-byte raw rows: the pitch and the second field's offset are multiples of them, vc2_raw_pic_offset)
     const bool vec_ok = FIRST ? (p.word_bytes == 2 && (pic_w & 7) == 0) : ((in_w & 7) == 0);
     constexpr int NLD = (WY * (WX / 8) + NT - 1) / NT;
     uint4 va[NLD], vb[NLD]; // FIRST: va = 8 samples; else va (, vb) = 8 coefficients of the level plane
@@ -416,8 +417,8 @@ __global__ __launch_bounds__(NTK<K>) void k_fwd_fast(const LevelParams p) {
       if (gy < 0 || gy >= in_h || gx0 + 8 <= 0 || gx0 >= in_w) continue;
       if constexpr (FIRST) {
         if (vec_ok && gx0 >= 0 && gx0 + 8 <= pic_w) {
-          const uint8_t *row = (const uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] +
-                               (size_t)min(gy, pic_h - 1) * pic_w * 2;
+          const uint8_t *row = (const uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +
+                               (size_t)min(gy, pic_h - 1) * p.raw_pitch[comp];
           va[it] = *(const uint4 *)(row + (size_t)gx0 * 2);
           kind[it] = 1;
         } else kind[it] = 2;
@@ -447,8 +448,8 @@ __global__ __launch_bounds__(NTK<K>) void k_fwd_fast(const LevelParams p) {
             s[2 * k + 1] = (int)(b & 0xFFFFu);
           }
         } else {
-          const uint8_t *row = (const uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] +
-                               (size_t)min(gy, pic_h - 1) * pic_w * p.word_bytes;
+          const uint8_t *row = (const uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +
+                               (size_t)min(gy, pic_h - 1) * p.raw_pitch[comp];
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             const int sx = min(max(gx0 + k, 0), pic_w - 1);
@@ -1021,7 +1022,7 @@ __global__ __launch_bounds__(NTK<K>) void k_inv_fast(const LevelParams p) {
 
   // ---- interleave, round, write (FINAL: clip + offset + justify + big-endian 16-bit words)
   const int lim_h = FINAL ? p.pic_h[comp] : out_h, lim_w = FINAL ? p.pic_w[comp] : out_w;
-  const bool vec_out = FINAL ? (p.word_bytes == 2 && (lim_w & 7) == 0) : ((out_w & 7) == 0);
+  const bool vec_out = FINAL ? (p.word_bytes == 2 && (lim_w & 7) == 0) : ((out_w & 7) == 0); // (as vec_ok in the forward kernel)
   for (int id = threadIdx.x; id < TY * (TX / 8); id += NT) {
     const int r = id / TXQ, ch = id % TXQ;
     const int gy = y0 + r, gx0 = x0 + 8 * ch;
@@ -1034,7 +1035,7 @@ __global__ __launch_bounds__(NTK<K>) void k_inv_fast(const LevelParams p) {
       for (int k = 0; k < 8; ++k) s[k] = (s[k] + (1 << (ACC > 0 ? ACC - 1 : 0))) >> ACC;
     }
     if constexpr (FINAL) {
-      uint8_t *row = (uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)gy * lim_w * p.word_bytes;
+      uint8_t *row = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) + (size_t)gy * p.raw_pitch[comp];
       unsigned u[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) u[k] = (unsigned)(min(max(s[k], p.clip_lo), p.clip_hi) + p.sample_offset) << p.sample_shift;

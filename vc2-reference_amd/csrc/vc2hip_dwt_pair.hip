@@ -129,19 +129,20 @@ __global__ __launch_bounds__(64, (pair_wpe<K>())) void k_fwd_pair(const PairPara
   const uint8_t *raw = nullptr;
   const ST *lvl = nullptr;
   const int32_t *lvl_w = nullptr;
-  if constexpr (FIRST) raw = (const uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 16;
+  if constexpr (FIRST) raw = (const uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) + (size_t)chunk * 16;
   else {
     lvl = (const ST *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 8;
     if constexpr (S_::narrow) lvl_w = p.plane_wide[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 8;
   }
   const int pic_h = FIRST ? p.pic_h[comp] : in_h;
+  const int rpw = FIRST ? p.raw_pitch[comp] >> 1 : in_w; // raw row pitch in 16-bit words (in_w, or two frame rows of a field)
   constexpr int NQ = (FIRST || S_::narrow) ? 1 : 2;
   uint4 pf[PFP][2][NQ];
   auto fetch = [&](int m, int slot) __attribute__((always_inline)) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int y = min(2 * m + h, pic_h - 1); // waveletPad: rows below the picture replicate its last row
-      if constexpr (FIRST) pf[slot][h][0] = *(const uint4 *)(raw + mul24z(y, in_w) * 2);
+      if constexpr (FIRST) pf[slot][h][0] = *(const uint4 *)(raw + mul24z(y, rpw) * 2);
       else {
         const ST *q = lvl + mul24z(y, in_w);
         pf[slot][h][0] = *(const uint4 *)q;
@@ -796,7 +797,7 @@ __global__ __launch_bounds__(64, (K == VC2HIP_DD137 || SPL2 ? 2 : VC2_PAIR_WPE_I
   uint8_t *rawo = nullptr; // (this picture's output plane; the lane's columns are part of the offset)
   ST *lvl = nullptr;
   int32_t *lvl_w = nullptr;
-  if constexpr (FINAL) rawo = (uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp];
+  if constexpr (FINAL) rawo = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic);
   else {
     lvl = (ST *)p.plane[comp] + (size_t)pic * p.plane_stride[comp];
     if constexpr (S_::narrow) lvl_w = p.plane_wide[comp] + (size_t)pic * p.plane_stride[comp];
@@ -836,7 +837,8 @@ __global__ __launch_bounds__(64, (K == VC2HIP_DD137 || SPL2 ? 2 : VC2_PAIR_WPE_I
   };
   auto put_out = [&](int y, const Pend &o) __attribute__((always_inline)) {
     if (!own || y >= lim_h) return;
-    const unsigned e = __umul24((unsigned)y, (unsigned)out_w) + ocol; // element (sample) index inside the plane
+    // element (sample) index inside the plane; FINAL: 16-bit word offset of the raw row (its pitch: two frame rows of a field)
+    const unsigned e = __umul24((unsigned)y, (unsigned)(FINAL ? p.raw_pitch[comp] >> 1 : out_w)) + ocol;
     if constexpr (FINAL) *(uint4 *)(rawo + (size_t)(e * 2u)) = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
     else if constexpr (S_::narrow) *(uint4 *)((char *)lvl + (size_t)(e * 2u)) = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
     else {
@@ -1147,6 +1149,7 @@ size_t vc2_pair_applicable(PairParams &pp, int kernel, bool edge, bool inverse, 
     if (p.tiles_x[c] == 0 || p.tiles_y[c] == 0) continue;
     const int w = p.in_w[c], h = p.in_h[c], fw = p.fw[c], fh = p.fh[c];
     if (w < VC2_STREAM_MIN_W || (w & 7) || (h & 3) || h < 48) return 0;
+    // (edge: 16-byte raw rows, so a field's base, one frame row from its frame's, keeps their alignment)
     if (edge && (p.word_bytes != 2 || p.pic_w[c] != w)) return 0;
     if (!pow2p(fw) || !pow2p(fh) || fw < 4 || fh < 4 || fw > 64 * 8) return 0;
     if (pb.fw[c] * 2 != fw || pb.fh[c] * 2 != fh || pb.in_w[c] * 2 != w || pb.in_h[c] * 2 != h) return 0;

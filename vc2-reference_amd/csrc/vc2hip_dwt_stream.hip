@@ -95,19 +95,20 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
   const uint8_t *raw = nullptr;
   const ST *lvl = nullptr;
   const int32_t *lvl_w = nullptr;
-  if constexpr (FIRST) raw = (const uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 16;
+  if constexpr (FIRST) raw = (const uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) + (size_t)chunk * 16;
   else {
     lvl = (const ST *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 8;
     if constexpr (S_::narrow) lvl_w = p.plane_wide[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 8;
   }
   const int pic_h = FIRST ? p.pic_h[comp] : in_h;
+  const int rpw = FIRST ? p.raw_pitch[comp] >> 1 : in_w; // raw row pitch in 16-bit words (in_w, or two frame rows of a field)
   constexpr int NQ = (FIRST || S_::narrow) ? 1 : 2; // 16-byte loads per row
   uint4 pf[PF][2][NQ];
   auto fetch = [&](int m, int slot) __attribute__((always_inline)) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int y = min(2 * m + h, pic_h - 1); // waveletPad: rows below the picture replicate its last row
-      if constexpr (FIRST) pf[slot][h][0] = *(const uint4 *)(raw + mul24z(y, in_w) * 2);
+      if constexpr (FIRST) pf[slot][h][0] = *(const uint4 *)(raw + mul24z(y, rpw) * 2);
       else {
         const ST *q = lvl + mul24z(y, in_w);
         pf[slot][h][0] = *(const uint4 *)q;
@@ -600,7 +601,8 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
   uint8_t *rawo = nullptr;
   ST *lvl = nullptr;
   int32_t *lvl_w = nullptr;
-  if constexpr (FINAL) rawo = (uint8_t *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 16;
+  const int rpw = FINAL ? p.raw_pitch[comp] >> 1 : out_w; // raw row pitch in 16-bit words (as the forward kernel)
+  if constexpr (FINAL) rawo = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) + (size_t)chunk * 16;
   else {
     lvl = (ST *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 8;
     if constexpr (S_::narrow) lvl_w = p.plane_wide[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 8;
@@ -643,9 +645,9 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
     if (!own || y >= lim_h) return;
     if constexpr (FINAL) {
 #if VC2_STREAM_NT_OUT
-      st_nt(rawo + mul24z(y, out_w) * 2, make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]));
+      st_nt(rawo + mul24z(y, rpw) * 2, make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]));
 #else
-      *(uint4 *)(rawo + mul24z(y, out_w) * 2) = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
+      *(uint4 *)(rawo + mul24z(y, rpw) * 2) = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
 #endif
     }
     else if constexpr (S_::narrow) *(uint4 *)(lvl + mul24z(y, out_w)) = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
@@ -913,6 +915,7 @@ size_t vc2_stream_level_applicable(LevelParams &p, int kernel, bool edge, bool i
       if (edge || rl == 8) return 0;
       p.st_tail = 1;
     }
+    // (edge: 16-byte raw rows, so a field's base, one frame row from its frame's, keeps their alignment)
     if (edge && (p.word_bytes != 2 || p.pic_w[c] != w)) return 0;
     if (!pow2i(fw) || !pow2i(fh) || fw < 8 || fh < 2 || fw > 64 * 8) return 0;
     const int bsh = fh / 2, bsw = fw / 2;

@@ -92,7 +92,10 @@ struct QuantTables {
 struct LevelParams {
   // input of a forward level / output of an inverse level
   void *plane[3];             // FIRST/FINAL: raw sample words, else LL_l plane (ST elements)
-  long long plane_stride[3];  // per picture, in bytes (raw) or elements (int32)
+  long long plane_stride[3];  // per picture, in bytes (raw) or elements (int32); field pictures (field_shift): per frame
+  int raw_pitch[3];           // FIRST/FINAL: bytes from one raw row to the next (pic_w * word_bytes; field pictures: two frame rows)
+  int field_step[3];          // FIRST/FINAL, field pictures: bytes from the first field's row 0 to the second field's (+-one frame row)
+  int field_shift;            // FIRST/FINAL: 1 = picture pic is field pic & 1 of frame pic >> 1 (plane[c]: the first field), 0 = progressive
   void *ll[3];                // LL_{l+1} plane, ST elements (forward: output unless LAST; inverse: input)
   long long ll_stride[3];     // per picture, elements
   void *store;                // coefficient store (int32_t or int16_t elements: the kernels' ST parameter)
@@ -134,6 +137,25 @@ struct LevelParams {
   // it, when the decoder keeps the level's bands as planes (BandPlanes below); -1: in the slice records
   long long bp_base[3];
   int bp8;                      // those planes hold one byte per coefficient (BandPlanes::bytes8)
+};
+
+// The one mapping from a picture of a batch to its raw words (every FIRST / FINAL address, both directions): progressive
+// pictures lie pic * stride apart; field pictures (field_shift 1) are fields of interleaved frames, picture pic the field
+// pic & 1 of frame pic >> 1, the second field field_step bytes from the first.  A field's rows are raw_pitch (two frame
+// rows) apart, so the two fields of a frame never share a byte.  field_step is +-one frame row: a multiple of 16 bytes
+// wherever the rows are (the 16-byte raw loads and stores of every kernel require that of the rows), so the second
+// field's base keeps every alignment the first one has.
+__host__ __device__ __forceinline__ long long vc2_raw_pic_offset(long long stride, int field_step, int field_shift, int pic) {
+  return (long long)(pic >> field_shift) * stride + (long long)(pic & field_shift) * field_step;
+}
+__host__ __device__ __forceinline__ long long vc2_raw_pic_offset(const LevelParams &p, int comp, int pic) {
+  return vc2_raw_pic_offset(p.plane_stride[comp], p.field_step[comp], p.field_shift, pic);
+}
+
+// the raw words of one component of a batch, as LevelParams holds them (plane_stride, raw_pitch, field_step, field_shift)
+struct RawPlane {
+  long long stride;
+  int pitch, field_step, field_shift;
 };
 
 // Two consecutive levels in one launch (vc2hip_dwt_pair.hip): `a` is the finer level exactly as the one-level kernels see

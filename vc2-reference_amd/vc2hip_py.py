@@ -73,6 +73,7 @@ EXPORTS = [
     "vc2hip_host_alloc", "vc2hip_host_free", "vc2hip_encode_picture_begin", "vc2hip_encode_picture_end",
     "vc2hip_decode_picture_begin", "vc2hip_decode_picture_end", "vc2hip_band_plane_bits", "vc2hip_dwt_launches",
     "vc2hip_picture_header", "vc2hip_stream_write_dev", "vc2hip_stream_read_dev",
+    "vc2hip_encode_fields_batch_dev", "vc2hip_decode_fields_batch_dev",
 ]
 
 
@@ -129,6 +130,10 @@ def load_library():
                                             C.POINTER(CodingParams), vp, C.c_size_t, vp]
     lib.vc2hip_decode_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat),
                                             C.POINTER(CodingParams), vp]
+    lib.vc2hip_encode_fields_batch_dev.argtypes = [vp, vp, C.c_int, C.POINTER(PictureFormat), C.c_int,
+                                                   C.POINTER(CodingParams), vp, C.c_size_t, vp]
+    lib.vc2hip_decode_fields_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat), C.c_int,
+                                                   C.POINTER(CodingParams), vp]
     lib.vc2hip_picture_header.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, u8p, C.c_size_t,
                                           C.POINTER(C.c_size_t)]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
@@ -378,6 +383,15 @@ class Vc2Hip:
     def decode_batch_dev(self, d_payload, stride, d_lens, n, fmt, cp, d_raw_out):
         self._chk(self.lib.vc2hip_decode_batch_dev(self.h, d_payload, stride, d_lens, n, C.byref(fmt),
                                                    C.byref(cp), d_raw_out))
+
+    # interlaced frames as field pictures: frame_fmt is the frame's format, cp one field's; 2 * n_frames slots in stream order
+    def encode_fields_batch_dev(self, d_frames, n_frames, frame_fmt, top_field_first, cp, d_payload, stride, d_lens):
+        self._chk(self.lib.vc2hip_encode_fields_batch_dev(self.h, d_frames, n_frames, C.byref(frame_fmt), int(top_field_first),
+                                                          C.byref(cp), d_payload, stride, d_lens))
+
+    def decode_fields_batch_dev(self, d_payload, stride, d_lens, n_frames, frame_fmt, top_field_first, cp, d_frames_out):
+        self._chk(self.lib.vc2hip_decode_fields_batch_dev(self.h, d_payload, stride, d_lens, n_frames, C.byref(frame_fmt),
+                                                          int(top_field_first), C.byref(cp), d_frames_out))
 
     # ---- VC-2 streams in device memory (the slots + lengths of the batch calls <-> picture data units)
     def picture_header(self, cp, major_version, picture_number):

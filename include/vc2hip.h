@@ -251,6 +251,31 @@ int vc2hip_encode_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
 int vc2hip_decode_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride,
                             const uint64_t *d_lens, int n, const vc2hip_picture_format *fmt,
                             const vc2hip_coding_params *cp, void *d_raw_out);
+/* Pictures at 1/2, 1/4, 1/8 ... size: the wavelet stream's own proxies.  The low-low band left when the inverse transform
+ * has run down to level drop_levels IS the picture at 1 / 2^drop_levels size, so the call decodes only the coarse head of
+ * every slice component (the coefficients are ordered coarse to fine; the component's length byte leads past the rest)
+ * and runs the depth - drop_levels coarsest inverse levels.  Per component, with the full decoder's dequantised
+ * coefficient plane P in the reference's in-place order: P[::2^k, ::2^k] is inverse-transformed with cp's wavelet at
+ * depth - k (rounding shifts included), cropped to (height >> k) x (width >> k), normalised by
+ * x = (x + (1 << (n - 1))) >> n with n = k for DD97, LeGall, DD137 and Haar1, 0 for Haar0, 2 k for Fidelity (the
+ * low-pass gain of the dropped levels: a constant picture comes back as that constant), then clipped and written as
+ * the full decoder writes samples.
+ *   fmt, cp     the CODED picture's, as for vc2hip_decode_batch_dev
+ *   drop_levels k, 1 ... cp->depth - 1
+ *   d_raw_out   n pictures of fmt with width >> k and height >> k (same chroma format, bit depth and word size), packed
+ *               back to back: vc2hip_raw_picture_bytes of that format each -- pictures vc2hip_encode_batch_dev could take
+ * Otherwise the batch calls' contract above, word for word: HQ_ConstQ, HQ_CBR and LD, all chroma formats, word_bytes
+ * 1 - 4; 16-byte alignment; asynchronous on the ctx stream, errors at vc2hip_sync; vc2hip_set_streams splits by
+ * pictures, results identical; a context may mix full and reduced calls and several drop_levels in any order.
+ * VC2HIP_EINVAL, nothing launched: drop_levels outside 1 ... depth - 1, Daub97 (its low-pass gain per level, about 3.03,
+ * is no power of two), a component whose width or height is not a multiple of 2^k, misaligned buffers.
+ * Slice data the call does not read -- the tail of every component, where the dropped levels' coefficients are -- is
+ * not validated: damage there that the full decoder would report or show goes unnoticed.
+ * vc2hip_dwt_launches counts levels in the coded picture: no entry of a reduced call is below level k.
+ * Extension, no counterpart in the reference. */
+int vc2hip_decode_reduced_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride,
+                                    const uint64_t *d_lens, int n, const vc2hip_picture_format *fmt,
+                                    const vc2hip_coding_params *cp, int drop_levels, void *d_raw_out);
 /* Interlaced frames coded as field pictures (EncodeStream -i): each frame is two pictures of half its height, numbered
  * per field, read from and written into the interleaved frames in place (no split or merge pass, no second raw buffer).
  *   d_frames    n_frames frames packed as encode_batch_dev's pictures; frame_fmt is the FRAME's format

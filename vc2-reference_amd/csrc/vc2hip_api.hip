@@ -40,7 +40,7 @@ int vc2_launch_plane_transform(Launcher &L, int kernel, int32_t *plane, long lon
 void vc2_launch_plane_ingest(Launcher &L, const void *raw, const RawPlane &rl, int pic_h, int pic_w, int word_bytes, int bit_depth,
                              int32_t *plane, long long plane_stride, int ph, int pw, int n, hipStream_t s);
 void vc2_launch_plane_emit(Launcher &L, const int32_t *plane, long long plane_stride, int pw, void *raw, const RawPlane &rl, int pic_h,
-                           int pic_w, int word_bytes, int bit_depth, int n, hipStream_t s);
+                           int pic_w, int word_bytes, int bit_depth, int n, hipStream_t s, int norm = 0);
 void vc2_launch_ll_into_plane(Launcher &L, const int32_t *ll, long long ll_stride, int llh, int llw, int32_t *plane, long long plane_stride,
                               int pw, int depth, int n, hipStream_t s);
 void vc2_launch_fill_i32(Launcher &L, int32_t *p, int32_t v, size_t n, hipStream_t s);
@@ -855,7 +855,9 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
                        const RawPlane *dst_l, bool dst_raw, const vc2hip_picture_format *f,
                        bool s16 = false, int32_t *store_wide = nullptr, const BandPlanes *bp = nullptr,
                        long long store_stride = 0, unsigned *stream_mask = nullptr, const HeadSplit *hs = nullptr, int head_level = 1 << 30,
-                       unsigned *fast_mask = nullptr, unsigned *tail_mask = nullptr) {
+                       unsigned *fast_mask = nullptr, unsigned *tail_mask = nullptr, int norm_shift = 0, int level_base = 0) {
+  // norm_shift, level_base (reduced pictures, decode_batch_common): g is the picture the kept levels make; the launch that
+  // writes the raw words normalises by norm_shift bits, and the launch record counts levels in the CODED picture
   if (tail_mask) *tail_mask = 0;
   if (stream_mask) *stream_mask = 0;
   if (fast_mask) *fast_mask = 0;
@@ -884,6 +886,7 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
       p.sample_offset = 1 << (f->bit_depth - 1);
       p.clip_lo = -(1 << (f->bit_depth - 1));
       p.clip_hi = (1 << (f->bit_depth - 1)) - 1;
+      p.norm_shift = norm_shift;
     }
   };
   for (int level = g.depth - 1; level >= 0; --level) {
@@ -907,7 +910,7 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
       if (lds) {
         int rc = vc2_launch_inverse_pair(c->L, kernel, fin_a, pp, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
-        record_dwt(c, true, level - 1, 2, VC2HIP_DWT_PAIR, fin_a, s16, pp.a.st_segmax, 0, false, n,
+        record_dwt(c, true, level_base + level - 1, 2, VC2HIP_DWT_PAIR, fin_a, s16, pp.a.st_segmax, 0, false, n,
                    std::max(band_plane_bits(pp.a), band_plane_bits(pp.b)));
         --level;
         continue;
@@ -922,7 +925,7 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
         if (stream_mask) { *stream_mask |= 1u << level; if (tail_mask && ps.st_tail) *tail_mask |= 1u << level; continue; }
         int rc = vc2_launch_inverse_stream(c->L, kernel, fin, ps, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
-        record_dwt(c, true, level, 1, VC2HIP_DWT_STREAM, fin, s16, ps.st_segmax, ps.st_tail, false, n, band_plane_bits(ps));
+        record_dwt(c, true, level_base + level, 1, VC2HIP_DWT_STREAM, fin, s16, ps.st_segmax, ps.st_tail, false, n, band_plane_bits(ps));
         continue;
       }
     }
@@ -931,14 +934,14 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
     if (!c->force_generic && vc2_fast_level_applicable(pf)) {
       int rc = vc2_launch_inverse_fast(c->L, kernel, fin, pf, n, s16, c->stream);
       if (rc) return set_err(c, rc, "invalid wavelet kernel");
-      record_dwt(c, true, level, 1, VC2HIP_DWT_FAST, fin, s16, 0, 0, vc2_fast_small_gather(pf), n, band_plane_bits(pf));
+      record_dwt(c, true, level_base + level, 1, VC2HIP_DWT_FAST, fin, s16, 0, 0, vc2_fast_small_gather(pf), n, band_plane_bits(pf));
       continue;
     }
     if (s16) return set_err(c, VC2HIP_EINVAL, "internal: 16-bit store without the fast level kernels");
     if (vc2_level_lds_bytes(kernel, p) > 160 * 1024) return set_err(c, VC2HIP_EINVAL, "slice too large for one LDS tile");
     int rc = vc2_launch_inverse_level(c->L, kernel, fin, p, n, c->stream);
     if (rc) return set_err(c, rc, "invalid wavelet kernel");
-    record_dwt(c, true, level, 1, VC2HIP_DWT_TILE, fin, false, 0, 0, false, n, band_plane_bits(p));
+    record_dwt(c, true, level_base + level, 1, VC2HIP_DWT_TILE, fin, false, 0, 0, false, n, band_plane_bits(p));
   }
   return VC2HIP_OK;
 }
@@ -1006,7 +1009,8 @@ static int plane_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const 
 // store (quantised) -> raw pictures (inverse), general geometry
 // ll (LD pictures): the DC-predicted LL reconstruction of every component, which replaces the plane's LL band
 static int plane_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, const int32_t *d_store, const int32_t *d_q, const int32_t *qm,
-                         void *const dst[3], const RawPlane ds[3], const vc2hip_picture_format *f, const LLPlanes *ll = nullptr) {
+                         void *const dst[3], const RawPlane ds[3], const vc2hip_picture_format *f, const LLPlanes *ll = nullptr,
+                         int norm_shift = 0, int level_base = 0) { // (the last two: as run_inverse's)
   int32_t *d_plane;
   int *d_qm;
   NEED(c, B_PLANE, plane_elems(g) * n * 4, d_plane);
@@ -1028,8 +1032,8 @@ static int plane_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, const 
                                      cg.pw, g.depth, n, c->stream);
     const int rc = vc2_launch_plane_transform(c->L, kernel, pl, ps, cg.ph, cg.pw, g.depth, true, n, c->stream);
     if (rc) return set_err(c, rc, "invalid wavelet kernel");
-    record_dwt(c, true, 0, g.depth, VC2HIP_DWT_PLANE, false, false, 0, 0, false, n);
-    vc2_launch_plane_emit(c->L, pl, ps, cg.pw, dst[k], ds[k], cg.h, cg.w, f->word_bytes, f->bit_depth, n, c->stream);
+    record_dwt(c, true, level_base, g.depth, VC2HIP_DWT_PLANE, false, false, 0, 0, false, n);
+    vc2_launch_plane_emit(c->L, pl, ps, cg.pw, dst[k], ds[k], cg.h, cg.w, f->word_bytes, f->bit_depth, n, c->stream, norm_shift);
   }
   return VC2HIP_OK;
 }
@@ -1712,7 +1716,7 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
 
 static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
                                const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out, bool ld,
-                               int fields = 1, int top_first = 1) {
+                               int fields = 1, int top_first = 1, int drop = 0) {
   if (!c || !d_payload || n < 1 || !f || !cp || !d_raw_out) return set_err(c, VC2HIP_EINVAL);
   if (((size_t)d_raw_out | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
     return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
@@ -1724,6 +1728,28 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
   if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
+  // A reduced picture (vc2hip_decode_reduced_batch_dev): without its `drop` finest levels the coded
+  // picture IS a picture of depth - drop levels whose planes and slices are 2^drop times smaller each way, on the same
+  // slice grid, with the first 3 (depth - drop) + 1 entries of the quantisation matrix (it is ordered coarse to fine).
+  // From here on g and f are that picture's: store layout, band planes, record heads and level kernels are planned for
+  // it as for any other.  What is left of the coded one: where a slice's bytes are (the index kernels walk length bytes,
+  // and the slice decoders find a component by them, read its first sh * sw coefficients and leave), and the low-pass
+  // gain of the dropped levels, which the launch that writes the raw words takes out (LevelParams::norm_shift).
+  vc2hip_picture_format fr;
+  int norm_shift = 0;
+  if (drop) { // (what the call refuses it has refused already: reduced_check)
+    if (fields != 1) return set_err(c, VC2HIP_EINVAL);
+    int h[3], w[3], ph[3], pw[3];
+    for (int k = 0; k < 3; ++k) {
+      const CompGeom &cg = g.c[k];
+      h[k] = cg.h >> drop; w[k] = cg.w >> drop; ph[k] = cg.ph >> drop; pw[k] = cg.pw >> drop;
+    }
+    if ((rc = make_geom(g, ph, pw, h, w, cp->depth - drop, cp->y_slices, cp->x_slices))) return set_err(c, rc);
+    fr = *f;
+    fr.width = f->width >> drop; fr.height = f->height >> drop;
+    f = &fr;
+    norm_shift = drop * (cp->kernel == VC2HIP_HAAR0 ? 0 : cp->kernel == VC2HIP_FIDELITY ? 2 : 1);
+  }
   const bool s16 = !ld && use_store16(c, g, cp->kernel);
   const void *dstc[3]; RawPlane ds[3];
   raw_planes(f, d_raw_out, fields, top_first, dstc, ds);
@@ -1884,7 +1910,7 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
       c->stat_n = std::min(n, 60);
       c->stat_n_total = n;
       c->stat_samples = 0;
-      for (int k = 0; k < 3; ++k) c->stat_samples += (double)g.c[k].h * g.c[k].w;
+      for (int k = 0; k < 3; ++k) c->stat_samples += (double)g.c[k].h * g.c[k].w * (1 << (2 * drop)); // (the payload is the coded picture's)
       c->stat_was8 = bp.bytes8 != 0;
       HIPCHK(c, hipMemcpyAsync(c->h_stat, c->d_stat, 8, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipMemcpyAsync(c->h_stat + 1, d_lens, (size_t)c->stat_n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1934,9 +1960,9 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
                        g.c[k].ph >> g.depth, g.c[k].pw >> g.depth, g.ys, g.xs, d_q, qm[0], (int32_t *)ll.p[g.depth][k],
                        ll.stride[g.depth][k], n, c->d_err, c->stream);
   }
-  if (plane_path) return plane_inverse(c, g, cp->kernel, n, d_store, d_q, qm, dst, ds, f, ld ? &ll : nullptr);
+  if (plane_path) return plane_inverse(c, g, cp->kernel, n, d_store, d_q, qm, dst, ds, f, ld ? &ll : nullptr, norm_shift, drop);
   return run_inverse(c, g, cp->kernel, n, d_store, d_q, qm, true, ld, ll, dst, ds, true, f, s16, d_storew, &bp, sstride, nullptr,
-                     hs.n[0] ? &hs : nullptr, head_level);
+                     hs.n[0] ? &hs : nullptr, head_level, nullptr, nullptr, norm_shift, drop);
 }
 
 extern "C" int vc2hip_band_plane_bits(const vc2hip_ctx *c) { return c ? c->last_plane_bits : 0; }
@@ -2071,6 +2097,48 @@ extern "C" int vc2hip_decode_batch_dev(vc2hip_ctx *c, const void *d_payload, siz
       });
   }
   return decode_batch_common(c, d_payload, payload_stride, d_lens, n, f, cp, d_raw_out, cp && cp->mode == VC2HIP_LD);
+}
+
+// Pictures at 1 / 2^drop_levels size (include/vc2hip.h): fmt and cp are the CODED picture's; the split over lanes is by
+// pictures, as the full decoder's, with the smaller pictures' size in the output
+extern "C" int vc2hip_decode_reduced_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
+                                               int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, int drop_levels,
+                                               void *d_raw_out) {
+  if (!c || !d_payload || n < 1 || !f || !cp || !d_raw_out) return set_err(c, VC2HIP_EINVAL);
+  if (((size_t)d_raw_out | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
+    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  // refused before anything is enqueued, on any lane
+  if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
+  if (drop_levels < 1 || drop_levels >= cp->depth)
+    return set_err(c, VC2HIP_EINVAL, "decode_reduced_batch_dev: drop_levels must be 1 ... depth - 1 (one transform level at least is kept)");
+  if (cp->kernel == VC2HIP_DAUB97)
+    return set_err(c, VC2HIP_EINVAL, "decode_reduced_batch_dev: Daub97's low-pass gain per level (about 3.03) is no power of two, so a shift cannot normalise its reduced pictures");
+  {
+    Geom g;
+    const int rc = picture_geom(g, f, cp, true);
+    if (rc) return set_err(c, rc);
+    for (int k = 0; k < 3; ++k)
+      if ((g.c[k].h | g.c[k].w) & ((1 << drop_levels) - 1))
+        return set_err(c, VC2HIP_EINVAL, "decode_reduced_batch_dev: every component's width and height must be a multiple of 2^drop_levels");
+  }
+  if (c->lanes.size() > 1 && n > 1 && !c->in_split) {
+    vc2hip_picture_format fr = *f;
+    fr.width = f->width >> drop_levels; fr.height = f->height >> drop_levels;
+    const size_t rb = vc2hip_raw_picture_bytes(&fr);
+    const uint8_t *out8 = (const uint8_t *)d_raw_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
+    return split_batch(c, n,
+      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
+        u.r[0] = {pay8 + (size_t)first * payload_stride, pay8 + (size_t)(first + count) * payload_stride};
+        u.r[1] = {len8 ? len8 + (size_t)first * 8 : nullptr, len8 ? len8 + (size_t)(first + count) * 8 : nullptr};
+        u.w[0] = {out8 + (size_t)first * rb, out8 + (size_t)(first + count) * rb}; u.w[1] = {nullptr, nullptr};
+      },
+      [&](vc2hip_ctx *l, int first, int count) {
+        return vc2hip_decode_reduced_batch_dev(l, pay8 + (size_t)first * payload_stride, payload_stride,
+                                               d_lens ? d_lens + first : nullptr, count, f, cp, drop_levels,
+                                               (uint8_t *)d_raw_out + (size_t)first * rb);
+      });
+  }
+  return decode_batch_common(c, d_payload, payload_stride, d_lens, n, f, cp, d_raw_out, cp->mode == VC2HIP_LD, 1, 1, drop_levels);
 }
 
 // Field pictures of interleaved frames (include/vc2hip.h): a field has the frame's format at half its height, so the

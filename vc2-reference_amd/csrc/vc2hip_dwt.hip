@@ -257,6 +257,7 @@ __global__ __launch_bounds__(256) void k_inv_level(const LevelParams p) {
     int v = w.plane(r & 1, c & 1)[((r + HY) >> 1) * w.wxp + ((c + HX) >> 1)];
     if (ACC) v = (v + (1 << (ACC - 1))) >> ACC;
     if constexpr (FINAL) {
+      if (p.norm_shift) v = vc2_norm(v, p.norm_shift); // a reduced picture
       v = min(max(v, p.clip_lo), p.clip_hi);
       const unsigned u = (unsigned)(v + p.sample_offset) << p.sample_shift;
       uint8_t *dst = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +

@@ -1037,6 +1037,10 @@ __global__ __launch_bounds__(NTK<K>) void k_inv_fast(const LevelParams p) {
     if constexpr (FINAL) {
       uint8_t *row = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) + (size_t)gy * p.raw_pitch[comp];
       unsigned u[8];
+      if (p.norm_shift) { // a reduced picture
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[k] = vc2_norm(s[k], p.norm_shift);
+      }
 #pragma unroll
       for (int k = 0; k < 8; ++k) u[k] = (unsigned)(min(max(s[k], p.clip_lo), p.clip_hi) + p.sample_offset) << p.sample_shift;
       if (vec_out && gx0 + 8 <= lim_w) {

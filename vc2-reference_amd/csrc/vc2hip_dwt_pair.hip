@@ -793,7 +793,7 @@ __global__ __launch_bounds__(64, (K == VC2HIP_DD137 || SPL2 ? 2 : VC2_PAIR_WPE_I
 
   // ---- output rows of level a (as k_inv_stream)
   const int lim_h = FINAL ? p.pic_h[comp] : out_h;
-  const int clip_lo = p.clip_lo, clip_hi = p.clip_hi, sample_offset = p.sample_offset, sample_shift = p.sample_shift;
+  const int clip_lo = p.clip_lo, clip_hi = p.clip_hi, sample_offset = p.sample_offset, sample_shift = p.sample_shift, norm_shift = p.norm_shift;
   uint8_t *rawo = nullptr; // (this picture's output plane; the lane's columns are part of the offset)
   ST *lvl = nullptr;
   int32_t *lvl_w = nullptr;
@@ -815,6 +815,10 @@ __global__ __launch_bounds__(64, (K == VC2HIP_DD137 || SPL2 ? 2 : VC2_PAIR_WPE_I
       for (int k = 0; k < 8; ++k) s[k] = (s[k] + (1 << (ACC > 0 ? ACC - 1 : 0))) >> ACC;
     }
     if constexpr (FINAL) {
+      if (norm_shift) { // a reduced picture
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[k] = vc2_norm(s[k], norm_shift);
+      }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const unsigned a = (unsigned)(min(max(s[2 * k], clip_lo), clip_hi) + sample_offset) << sample_shift;

@@ -28,10 +28,12 @@ __global__ void k_plane_ingest(const uint8_t *raw, long long raw_stride, int raw
 }
 // int32 plane -> raw planar words, clipped (Picture.cpp:284-292, Arrays.cpp:381-426); the padding is cropped
 __global__ void k_plane_emit(const int32_t *plane, long long plane_stride, int pw, uint8_t *raw, long long raw_stride, int raw_pitch,
-                             int field_step, int field_shift, int pic_h, int pic_w, int word_bytes, int shift, int offset, int lo, int hi) {
+                             int field_step, int field_shift, int pic_h, int pic_w, int word_bytes, int shift, int offset, int lo, int hi, int norm) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, pic = blockIdx.z;
   if (x >= pic_w) return;
-  const int v = min(max(plane[(size_t)pic * plane_stride + (size_t)y * pw + x], lo), hi);
+  int v = plane[(size_t)pic * plane_stride + (size_t)y * pw + x];
+  if (norm) v = vc2_norm(v, norm); // a reduced picture (LevelParams::norm_shift)
+  v = min(max(v, lo), hi);
   const unsigned u = (unsigned)(v + offset) << shift;
   uint8_t *q = raw + vc2_raw_pic_offset(raw_stride, field_step, field_shift, pic) + (size_t)y * raw_pitch + (size_t)x * word_bytes;
   for (int b = 0; b < word_bytes; ++b) q[b] = (uint8_t)(u >> (8 * (word_bytes - 1 - b)));
@@ -140,9 +142,9 @@ void vc2_launch_plane_ingest(Launcher &L, const void *raw, const RawPlane &rl, i
   vc2_prof_end(L, s);
 }
 void vc2_launch_plane_emit(Launcher &L, const int32_t *plane, long long plane_stride, int pw, void *raw, const RawPlane &rl, int pic_h,
-                           int pic_w, int word_bytes, int bit_depth, int n, hipStream_t s) {
+                           int pic_w, int word_bytes, int bit_depth, int n, hipStream_t s, int norm) {
   vc2_prof_begin(L, "plane_emit", s);
   VC2_LAUNCH(L, k_plane_emit, dim3((pic_w + 127) / 128, pic_h, n), dim3(128), 0, s, plane, plane_stride, pw, (uint8_t *)raw, rl.stride,
-             rl.pitch, rl.field_step, rl.field_shift, pic_h, pic_w, word_bytes, 8 * word_bytes - bit_depth, 1 << (bit_depth - 1), -(1 << (bit_depth - 1)), (1 << (bit_depth - 1)) - 1);
+             rl.pitch, rl.field_step, rl.field_shift, pic_h, pic_w, word_bytes, 8 * word_bytes - bit_depth, 1 << (bit_depth - 1), -(1 << (bit_depth - 1)), (1 << (bit_depth - 1)) - 1, norm);
   vc2_prof_end(L, s);
 }

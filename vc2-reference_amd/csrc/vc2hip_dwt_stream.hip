@@ -302,9 +302,13 @@ __device__ __forceinline__ int dequant_full(int v, int qf, int off) { // scale()
 // BP8 (round 5): the level's band planes hold ONE BYTE per coefficient (vc2hip_internal.h BandPlanes::bytes8: quantised
 // coefficients are small; -128 is the sentinel, the value then sits in the wide array at the element's index as for the
 // 16-bit sentinel).  This kernel runs at the memory system's pace: its band rows are half of what it reads.
-template <int K, bool FINAL, class ST, bool TAIL = false, bool BP8 = false>
+// NORM: the FINAL level of a reduced picture (LevelParams::norm_shift).  Instantiations of their own: a test of the
+// argument in the output row, wave-uniform as it is, cost the full decoder's FINAL kernels a register or more each, some
+// a wavefront per SIMD or scratch -- so theirs are compiled without it.
+template <int K, bool FINAL, class ST, bool TAIL = false, bool BP8 = false, bool NORM = false>
 __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) void k_inv_stream(const LevelParams p) {
   using S_ = St<ST>;
+  static_assert(!NORM || FINAL, "only raw words are normalised");
   static_assert(!BP8 || (S_::narrow && !TAIL), "byte planes: with the 16-bit store, whole blocks");
   using VE = VEng<K, true>;
   using T = typename VE::T;
@@ -621,6 +625,10 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
       for (int k = 0; k < 8; ++k) s[k] = (s[k] + (1 << (ACC > 0 ? ACC - 1 : 0))) >> ACC;
     }
     if constexpr (FINAL) {
+      if constexpr (NORM) { // a reduced picture (norm_shift > 0: the host launches this form for nothing else)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[k] = vc2_norm(s[k], p.norm_shift);
+      }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const unsigned a = (unsigned)(min(max(s[2 * k], p.clip_lo), p.clip_hi) + p.sample_offset) << p.sample_shift;
@@ -756,6 +764,22 @@ void launch_stream(Launcher &L, const LevelParams &p, int n_pictures, size_t lds
 #endif
   if constexpr (INV) {
     vc2_prof_begin(L, EDGE ? "idwt_level_final" : "idwt_level", s);
+    if constexpr (EDGE && !TAIL && K != VC2HIP_DAUB97) { // (an edge level never takes the TAIL form; Daub97 has no reduced pictures)
+      if (pw.norm_shift) {
+        if constexpr (std::is_same<ST, int16_t>::value) {
+          if (pw.bp8) {
+            vc2_allow_lds((const void *)k_inv_stream<K, true, ST, false, true, true>, std::max<size_t>(64 * 1024, lds_wg));
+            VC2_LAUNCH(L, (k_inv_stream<K, true, ST, false, true, true>), grid, block, lds_wg, s, pw);
+            vc2_prof_end(L, s);
+            return;
+          }
+        }
+        vc2_allow_lds((const void *)k_inv_stream<K, true, ST, false, false, true>, std::max<size_t>(64 * 1024, lds_wg));
+        VC2_LAUNCH(L, (k_inv_stream<K, true, ST, false, false, true>), grid, block, lds_wg, s, pw);
+        vc2_prof_end(L, s);
+        return;
+      }
+    }
     if constexpr (std::is_same<ST, int16_t>::value && !TAIL) {
       if (pw.bp8) {
         vc2_allow_lds((const void *)k_inv_stream<K, EDGE, ST, TAIL, true>, std::max<size_t>(64 * 1024, lds_wg));

@@ -137,7 +137,12 @@ struct LevelParams {
   // it, when the decoder keeps the level's bands as planes (BandPlanes below); -1: in the slice records
   long long bp_base[3];
   int bp8;                      // those planes hold one byte per coefficient (BandPlanes::bytes8)
+  // FINAL, reduced pictures (vc2hip_decode_reduced_batch_dev): the low-pass gain of the dropped levels leaves before the
+  // clip, x = (x + (1 << (norm_shift - 1))) >> norm_shift; 0: the full decoder (the test is wave-uniform)
+  int norm_shift;
 };
+// the normalisation of a reduced picture's samples (LevelParams::norm_shift); n > 0
+__device__ __forceinline__ int vc2_norm(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
 // The one mapping from a picture of a batch to its raw words (every FIRST / FINAL address, both directions): progressive
 // pictures lie pic * stride apart; field pictures (field_shift 1) are fields of interleaved frames, picture pic the field

@@ -73,7 +73,7 @@ EXPORTS = [
     "vc2hip_host_alloc", "vc2hip_host_free", "vc2hip_encode_picture_begin", "vc2hip_encode_picture_end",
     "vc2hip_decode_picture_begin", "vc2hip_decode_picture_end", "vc2hip_band_plane_bits", "vc2hip_dwt_launches",
     "vc2hip_picture_header", "vc2hip_stream_write_dev", "vc2hip_stream_read_dev",
-    "vc2hip_encode_fields_batch_dev", "vc2hip_decode_fields_batch_dev",
+    "vc2hip_encode_fields_batch_dev", "vc2hip_decode_fields_batch_dev", "vc2hip_decode_reduced_batch_dev",
 ]
 
 
@@ -134,6 +134,8 @@ def load_library():
                                                    C.POINTER(CodingParams), vp, C.c_size_t, vp]
     lib.vc2hip_decode_fields_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat), C.c_int,
                                                    C.POINTER(CodingParams), vp]
+    lib.vc2hip_decode_reduced_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat),
+                                                    C.POINTER(CodingParams), C.c_int, vp]
     lib.vc2hip_picture_header.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, u8p, C.c_size_t,
                                           C.POINTER(C.c_size_t)]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
@@ -163,6 +165,12 @@ def load_library():
 
 def picture_format(width, height, cf, bits, word_bytes=2, chroma_bits=0):
     return PictureFormat(width, height, CF[cf], bits, word_bytes, chroma_bits)
+
+
+def reduced_format(fmt, drop_levels):
+    """the format of the pictures vc2hip_decode_reduced_batch_dev writes for coded pictures of fmt"""
+    return PictureFormat(fmt.width >> drop_levels, fmt.height >> drop_levels, fmt.chroma_format, fmt.bit_depth, fmt.word_bytes,
+                         fmt.chroma_bit_depth)
 
 
 def coding_params(lib, fmt, kernel, depth, u, a, mode="HQ_ConstQ", q=0, s=0, prefix=0, scalar=1):
@@ -383,6 +391,11 @@ class Vc2Hip:
     def decode_batch_dev(self, d_payload, stride, d_lens, n, fmt, cp, d_raw_out):
         self._chk(self.lib.vc2hip_decode_batch_dev(self.h, d_payload, stride, d_lens, n, C.byref(fmt),
                                                    C.byref(cp), d_raw_out))
+
+    # pictures at 1 / 2**drop_levels size: fmt and cp are the coded picture's, d_raw_out takes reduced_format(fmt, drop_levels) pictures
+    def decode_reduced_batch_dev(self, d_payload, stride, d_lens, n, fmt, cp, drop_levels, d_raw_out):
+        self._chk(self.lib.vc2hip_decode_reduced_batch_dev(self.h, d_payload, stride, d_lens, n, C.byref(fmt), C.byref(cp),
+                                                           drop_levels, d_raw_out))
 
     # interlaced frames as field pictures: frame_fmt is the frame's format, cp one field's; 2 * n_frames slots in stream order
     def encode_fields_batch_dev(self, d_frames, n_frames, frame_fmt, top_field_first, cp, d_payload, stride, d_lens):

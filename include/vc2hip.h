@@ -276,6 +276,46 @@ int vc2hip_decode_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t paylo
 int vc2hip_decode_reduced_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride,
                                     const uint64_t *d_lens, int n, const vc2hip_picture_format *fmt,
                                     const vc2hip_coding_params *cp, int drop_levels, void *d_raw_out);
+/* The encode of vc2hip_encode_batch_dev together with what it did to the pictures: the picture the decoder will show, the
+ * squared error against the input and the quantiser indices -- EncodeStream -o Decoded, -o PSNR and -o Indices
+ * (EncodeStream.cpp:649-767) for pictures in device memory.  Entropy coding is lossless, so the decoded picture follows from
+ * the quantised coefficients: the call quantises the transform coefficients it holds, dequantises and inverse-transforms
+ * them.  It never decodes its own payload (no slice index, no slice decoder), and without d_payload it runs no slice coder.
+ *   d_payload, payload_stride, d_lens   all three, or NULL / 0 / NULL (no slice coding).  Byte for byte those of
+ *               vc2hip_encode_batch_dev with the same arguments; the same capacity rules and errors
+ *   d_recon     n pictures of fmt, packed as d_raw, or NULL: byte for byte what vc2hip_decode_batch_dev writes when given this
+ *               call's payload with the same fmt and cp (clipped, offset, MSB-justified big-endian words: pictures
+ *               vc2hip_encode_batch_dev could take again), whether or not the payload was asked for
+ *   d_sse       n x 3 uint64 (Y, U, V), or NULL; needs d_recon.  d_sse[3 i + c] = the sum over component c's unpadded h x w
+ *               samples of picture i of (a - b)^2, a and b the input's and the reconstruction's sample values
+ *               word >> (8 * word_bytes - bit_depth) (the offset cancels; input bits below the depth are ignored, as the
+ *               ingest ignores them): the reference's YSS / USS / VSS (EncodeStream.cpp:714, :728, :740) per picture, in
+ *               unsigned 64-bit arithmetic.  A sum cannot wrap while h * w * (2^bit_depth - 1)^2 < 2^64: up to 16 bits for
+ *               every component of fewer than 2^32 samples, up to 20 bits for 2^24 samples (4096 x 4096), at 32 bits never
+ *               safe beyond one sample.  vc2hip_py.psnr_db turns a sum into the figure of -o PSNR
+ *   d_qidx      n x y_slices * x_slices int32, raster order, or NULL: the index of every slice as the encoder used it --
+ *               q_index everywhere for HQ_ConstQ, the result of the search for HQ_CBR and LD
+ * All modes, wavelets (Daub97 included), chroma formats, word_bytes 1 - 4, padded sizes, prefix and scalar; every context flag
+ * gives the same bytes.  LD: the reconstruction is the DECODER's (DC-predicted LL band).  The reference's own -o Decoded
+ * dequantises LD pictures without the prediction (EncodeStream.cpp:651); this call does not copy that.
+ * Otherwise the batch calls' contract above, word for word: 16-byte aligned d_raw, d_payload, d_recon and stride, 8-byte
+ * aligned d_lens and d_sse, 4-byte aligned d_qidx; asynchronous on the ctx stream; nothing allocated, copied to the host or
+ * waited for once the context has seen the geometry and n; vc2hip_set_streams splits by pictures, results identical; a
+ * context may mix this call with every other batch call in any order.
+ * VC2HIP_EINVAL, nothing launched, no output byte touched: no output asked for; d_sse without d_recon; payload, stride and
+ * lens not all given or all absent; d_recon overlapping d_raw (the error sum reads the input after the reconstruction is
+ * written); misalignment; with d_recon, fmt->chroma_bit_depth other than 0 or bit_depth (the decoder has one depth) or a
+ * size whose padded chroma planes the decoder derives differently from the encoder (no decoder shows that picture);
+ * everything vc2hip_encode_batch_dev refuses.
+ * Errors the kernels find (VC2HIP_ESCALAR, VC2HIP_ECODE32, VC2HIP_EQINDEX, VC2HIP_ECBR_*, VC2HIP_ELD_TOOBIG) surface at
+ * vc2hip_sync exactly as for vc2hip_encode_batch_dev on the same input, also when no payload was asked for (the
+ * reconstruction claims to be that of a payload that could not have been written); d_recon and d_sse are unspecified then.
+ * vc2hip_dwt_launches holds the call's forward launches, then its inverse launches.
+ * Extension, no counterpart in the reference's Library. */
+int vc2hip_encode_recon_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
+                                  const vc2hip_picture_format *fmt, const vc2hip_coding_params *cp,
+                                  void *d_payload, size_t payload_stride, uint64_t *d_lens,
+                                  void *d_recon, uint64_t *d_sse, int32_t *d_qidx);
 /* Interlaced frames coded as field pictures (EncodeStream -i): each frame is two pictures of half its height, numbered
  * per field, read from and written into the interleaved frames in place (no split or merge pass, no second raw buffer).
  *   d_frames    n_frames frames packed as encode_batch_dev's pictures; frame_fmt is the FRAME's format

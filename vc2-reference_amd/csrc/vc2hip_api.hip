@@ -128,7 +128,9 @@ struct Buf {
   size_t cap = 0;
 };
 enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS, B_LENS, B_PAYLOAD,
-       B_INDEX, B_PLANE, B_PLANE2, B_CBRB, B_CBRO, B_QM, B_UNITS, B_SEGS, B_COUNT };
+       B_INDEX, B_PLANE, B_PLANE2, B_CBRB, B_CBRO, B_QM, B_UNITS, B_SEGS,
+       B_RSTORE, B_RSTOREW, // encode_recon_batch_dev: the quantised coefficients in the decoder's layout
+       B_COUNT };
 
 struct vc2hip_ctx {
   int device = 0;
@@ -189,7 +191,8 @@ struct vc2hip_ctx {
   std::vector<hipEvent_t> join_ev;    // end of lane i's latest sub-batch
   bool lanes_pending = false;         // `stream` has not yet been made to wait for the lanes' latest sub-batches
   struct Range { const uint8_t *lo, *hi; };
-  struct LaneUse { Range r[2], w[2]; bool valid = false; };
+  enum { LANE_RANGES = 5 };            // caller buffers one call reads / writes (encode_recon_batch_dev writes five)
+  struct LaneUse { Range r[LANE_RANGES], w[LANE_RANGES]; bool valid = false; };
   std::vector<LaneUse> lane_use;      // what lane i's latest sub-batch read and wrote (caller buffers)
   std::vector<ProfEntry> merged; // profile of this context and its lanes, rebuilt by vc2hip_profile_count
   // pipelined picture calls: VC2HIP_MAX_INFLIGHT slots, each a child context (own stream and workspace)
@@ -391,6 +394,7 @@ static int create_common(int device, hipStream_t stream, bool own, vc2hip_ctx **
   vc2_upload_tables_fast(t, c->stream);
   vc2_upload_tables_pair(t, c->stream);
   vc2_upload_tables_stream(t, c->stream);
+  vc2_upload_tables_recon(t, c->stream);
   vc2_upload_vlc_lut(c->stream);
   vc2_upload_unpack_lut(c->stream);
   if (hipStreamSynchronize(c->stream) != hipSuccess) { delete c; return VC2HIP_EHIP; }
@@ -522,8 +526,8 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
       const vc2hip_ctx::LaneUse &p = c->lane_use[j];
       if ((int)j == i || !p.valid) continue;
       bool dep = false;
-      for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b)
+      for (int a = 0; a < vc2hip_ctx::LANE_RANGES; ++a)
+        for (int b = 0; b < vc2hip_ctx::LANE_RANGES; ++b)
           dep |= overlap(cur[i].r[a], p.w[b]) || overlap(cur[i].w[a], p.w[b]) || overlap(cur[i].w[a], p.r[b]);
       if (dep) HIPCHK(c, hipStreamWaitEvent(l->stream, c->join_ev[j], 0));
     }
@@ -1605,8 +1609,98 @@ static void raw_planes(const vc2hip_picture_format *f, const void *base, int fie
   }
 }
 
+// The decoder's store for n pictures of g: the slice records, behind them the band planes of the finest levels and the
+// record heads of the deep ones (planned by dry runs of run_inverse: nothing is launched).  decode_batch_common plans the
+// store the slice decoders fill, encode_recon_batch_dev the one the requantise kernel fills for the same inverse kernels.
+struct DecoderLayout {
+  BandPlanes bp;
+  HeadSplit hs;
+  int head_level;    // first level that reads the record heads (1 << 30: none)
+  long long sstride; // elements per picture
+  unsigned tails;    // levels whose streaming kernel is the TAIL instantiation
+};
+static void plan_decoder_layout(vc2hip_ctx *c, const Geom &g, int kernel, int n, bool ld, const int32_t *qm, void *const dst[3], const RawPlane ds[3],
+                                const vc2hip_picture_format *f, bool s16, bool plane_path, DecoderLayout &lay) {
+  // Band planes (vc2hip_internal.h): the finest levels, as long as they go through the streaming inverse kernel, a
+  // slice's block row in them is at least 4 coefficients (8: rows that keep 16-byte pieces aligned) and they are not
+  // the level whose LL comes from the store.  16-bit store only (the int32 store is the fallback decoder's).
+  BandPlanes &bp = lay.bp;
+  HeadSplit &hs = lay.hs;
+  memset(&lay, 0, sizeof lay);
+  const int ns = g.ys * g.xs;
+  int head_level = 1 << 30;
+  long long sstride = (long long)ns * g.slice_coefs; // elements per picture: slice records, then band planes
+  if (s16 && !plane_path && c->allow_planes) {
+    unsigned mask = 0;
+    LLPlanes none;
+    memset(&none, 0, sizeof none);
+    unsigned &tails = lay.tails;
+    (void)run_inverse(c, g, kernel, n, nullptr, nullptr, qm, true, ld, none, dst, ds, true, f, s16, nullptr, nullptr, 0, &mask, nullptr, 1 << 30,
+                      nullptr, &tails);
+    for (int k = 0; k < 3; ++k) bp.from[k] = g.c[k].ph ? g.c[k].sh * g.c[k].sw : 0;
+    for (int l = 0; l < VC2_BP_MAX && l < g.depth - 1 && (mask >> l & 1); ++l) {
+      bool ok = true;
+      for (int k = 0; k < 3 && ok; ++k) {
+        const CompGeom &cg = g.c[k];
+        if (!cg.ph) continue;
+        const int bsh = (cg.sh >> l) / 2, bsw = (cg.sw >> l) / 2, ow = (cg.pw >> l) / 2;
+        ok = bsh >= 1 && bsw >= 4 && (bsh & (bsh - 1)) == 0 && (bsw & (bsw - 1)) == 0 && ow % (bsw >= 8 ? 8 : 4) == 0 &&
+             (bsh * bsw) % 8 == 0;
+      }
+      if (!ok) break;
+      for (int k = 0; k < 3; ++k) {
+        const CompGeom &cg = g.c[k];
+        if (!cg.ph) continue;
+        const int bsh = (cg.sh >> l) / 2, bsw = (cg.sw >> l) / 2;
+        bp.np[k][l] = (cg.ph >> l) / 2; bp.ow[k][l] = (cg.pw >> l) / 2;
+        bp.lbsh[k][l] = 31 - __builtin_clz(bsh); bp.lbsw[k][l] = 31 - __builtin_clz(bsw);
+        bp.base[k][l] = sstride;
+        sstride += ((long long)3 * bp.np[k][l] * bp.ow[k][l] + 7) & ~7ll;
+        bp.from[k] -= 3 * bsh * bsw;
+      }
+      bp.levels = l + 1;
+    }
+    if (sstride >= (1ll << 31)) { memset(&bp, 0, sizeof bp); sstride = (long long)ns * g.slice_coefs; } // 32-bit element offsets
+  }
+  // Record heads (HeadSplit, vc2hip_internal.h): the levels below the streaming ones, when all of them run on the tile
+  // kernels, read their coefficients from dense per-component arrays behind the records (and band planes)
+  if (s16 && !plane_path && c->allow_heads) {
+    unsigned smask = 0, fmask = 0;
+    LLPlanes none;
+    memset(&none, 0, sizeof none);
+    (void)run_inverse(c, g, kernel, n, nullptr, nullptr, qm, true, ld, none, dst, ds, true, f, s16, nullptr, nullptr, 0, &smask, nullptr, 1 << 30, &fmask);
+    int ls = g.depth; // first level of the run of tile-kernel levels that reaches the deepest one
+    while (ls > 0 && !(smask >> (ls - 1) & 1) && (fmask >> (ls - 1) & 1)) --ls;
+    bool ok = ls >= 1 && ls < g.depth && ls >= bp.levels; // (level 0 keeps its bands where the final kernels expect them)
+    for (int k = 0; k < 3 && ok; ++k) {
+      if (!g.c[k].ph) continue;
+      const int hn = (g.c[k].sh >> ls) * (g.c[k].sw >> ls);
+      ok = hn >= 8 && hn % 8 == 0 && hn <= bp.from[k];
+    }
+    if (ok) {
+      long long at = sstride;
+      for (int k = 0; k < 3; ++k) {
+        if (!g.c[k].ph) continue;
+        hs.n[k] = (g.c[k].sh >> ls) * (g.c[k].sw >> ls);
+        hs.base[k] = at;
+        at += ((long long)ns * hs.n[k] + 7) & ~7ll;
+      }
+      if (at < (1ll << 31)) { sstride = at; head_level = ls; } else memset(&hs, 0, sizeof hs);
+    }
+  }
+  lay.head_level = head_level;
+  lay.sstride = sstride;
+}
+
+// what vc2hip_encode_recon_batch_dev asks for beyond (or instead of) the payload
+struct ReconOut {
+  void *recon;     // the decoder's picture, or null
+  uint64_t *sse;   // n x 3 sums of squared differences against d_raw, or null
+  int32_t *qidx;   // n x slices, or null
+};
 static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int top_first, int n, const vc2hip_picture_format *f,
-                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens);
+                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
+                               const ReconOut *ro = nullptr);
 
 extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
                                        const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride,
@@ -1631,9 +1725,64 @@ extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, 
   return encode_batch_common(c, d_raw, 1, 1, n, f, cp, d_payload, payload_stride, d_lens);
 }
 
+static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f, const int32_t *qm,
+                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const void *d_raw, const ReconOut &ro,
+                     const int32_t *d_cb, bool check, const LdEncParams *ld);
+
+extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
+                                             const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
+                                             void *d_recon, uint64_t *d_sse, int32_t *d_qidx) {
+  if (!c || !d_raw || n < 1 || !f || !cp) return set_err(c, VC2HIP_EINVAL);
+  if (!d_payload && !d_recon && !d_sse && !d_qidx) return set_err(c, VC2HIP_EINVAL, "no output asked for");
+  if (d_sse && !d_recon) return set_err(c, VC2HIP_EINVAL, "d_sse needs d_recon");
+  if ((d_payload != nullptr) != (payload_stride != 0) || (d_payload != nullptr) != (d_lens != nullptr))
+    return set_err(c, VC2HIP_EINVAL, "d_payload, payload_stride and d_lens: all or none");
+  if (((size_t)d_raw | (size_t)d_payload | (size_t)d_recon | payload_stride) & 15 || (((size_t)d_lens | (size_t)d_sse) & 7) || ((size_t)d_qidx & 3))
+    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  Geom ge;
+  if (picture_geom(ge, f, cp, false)) return set_err(c, VC2HIP_EINVAL);
+  const size_t rb = vc2hip_raw_picture_bytes(f);
+  const int ns = ge.ys * ge.xs;
+  const uint8_t *raw8 = (const uint8_t *)d_raw;
+  uint8_t *rec8 = (uint8_t *)d_recon;
+  if (d_recon) {
+    if (rec8 < raw8 + (size_t)n * rb && raw8 < rec8 + (size_t)n * rb)
+      return set_err(c, VC2HIP_EINVAL, "d_recon overlaps d_raw (the squared error reads the input after the reconstruction is written)");
+    if (f->chroma_bit_depth && f->chroma_bit_depth != f->bit_depth)
+      return set_err(c, VC2HIP_EINVAL, "the decoder has one bit depth: chroma_bit_depth must be 0 or bit_depth with d_recon");
+    Geom gd; // (the decoder derives the chroma planes from the padded luma plane, DecodeStream.cpp:483-498)
+    if (picture_geom(gd, f, cp, true)) return set_err(c, VC2HIP_EINVAL);
+    for (int k = 0; k < 3; ++k)
+      if (gd.c[k].ph != ge.c[k].ph || gd.c[k].pw != ge.c[k].pw)
+        return set_err(c, VC2HIP_EINVAL, "the decoder's padded chroma planes differ from the encoder's: no decoder shows this picture");
+  }
+  if (c->lanes.size() > 1 && n > 1 && !c->in_split) {
+    uint8_t *pay8 = (uint8_t *)d_payload;
+    auto rng = [](const void *p, size_t first, size_t count, size_t each) {
+      const uint8_t *q = (const uint8_t *)p;
+      return q ? vc2hip_ctx::Range{q + first * each, q + (first + count) * each} : vc2hip_ctx::Range{nullptr, nullptr};
+    };
+    return split_batch(c, n,
+      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
+        u.r[0] = rng(d_raw, first, count, rb);
+        u.w[0] = rng(d_payload, first, count, payload_stride); u.w[1] = rng(d_lens, first, count, 8);
+        u.w[2] = rng(d_recon, first, count, rb); u.w[3] = rng(d_sse, first, count, 24); u.w[4] = rng(d_qidx, first, count, (size_t)ns * 4);
+      },
+      [&](vc2hip_ctx *l, int first, int count) {
+        return vc2hip_encode_recon_batch_dev(l, raw8 + (size_t)first * rb, count, f, cp, pay8 ? pay8 + (size_t)first * payload_stride : nullptr,
+                                             payload_stride, d_lens ? d_lens + first : nullptr, rec8 ? rec8 + (size_t)first * rb : nullptr,
+                                             d_sse ? d_sse + 3 * (size_t)first : nullptr, d_qidx ? d_qidx + (size_t)first * ns : nullptr);
+      });
+  }
+  const ReconOut ro = {d_recon, d_sse, d_qidx};
+  return encode_batch_common(c, d_raw, 1, 1, n, f, cp, d_payload, payload_stride, d_lens, &ro);
+}
+
 // n pictures of format f (raw_planes: progressive pictures, or the fields of interleaved frames) -> payload slots
+// ro (vc2hip_encode_recon_batch_dev): d_payload may be null -- no slice coder runs then -- and run_recon follows the coder
 static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int top_first, int n, const vc2hip_picture_format *f,
-                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens) {
+                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
+                               const ReconOut *ro) {
   if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD) return set_err(c, VC2HIP_EINVAL);
   if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
   if (cp->mode != VC2HIP_LD && (cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
@@ -1672,16 +1821,18 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
       c->cbr_total = total;
     }
     d_cb = (int32_t *)c->buf[B_CBRB].p; d_co = (uint32_t *)c->buf[B_CBRO].p; total = c->cbr_total;
-    if (total > payload_stride) return set_err(c, VC2HIP_ECAP);
+    if (d_payload && total > payload_stride) return set_err(c, VC2HIP_ECAP);
     LdEncParams p;
     c->ld_batch = n;
     if ((rc = fill_ld_enc(c, p, g, d_store, d_q, qm, ll, d_cb, d_co, cp->compressed_bytes / ns + 5, (uint8_t *)d_payload,
                           (long long)payload_stride))) return rc;
     p.search = 1;
     vc2_launch_ld_quantise(c->L, p, n, c->stream);
-    vc2_launch_ld_pack(c->L, p, n, c->stream);
-    vc2_launch_fill_u64(c->L, (unsigned long long *)d_lens, total, (size_t)n, c->stream);
-    return VC2HIP_OK;
+    if (d_payload) {
+      vc2_launch_ld_pack(c->L, p, n, c->stream);
+      vc2_launch_fill_u64(c->L, (unsigned long long *)d_lens, total, (size_t)n, c->stream);
+    }
+    return ro ? run_recon(c, g, cp, n, f, qm, false, d_store, nullptr, d_q, ll, d_raw, *ro, d_cb, !d_payload, &p) : VC2HIP_OK;
   }
   if (cp->mode == VC2HIP_HQ_CBR) {
       const int key[5] = {g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix};
@@ -1693,7 +1844,7 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
       c->cbr_total = total;
     }
     d_cb = (int32_t *)c->buf[B_CBRB].p; d_co = (uint32_t *)c->buf[B_CBRO].p; total = c->cbr_total;
-    if (total > payload_stride) return set_err(c, VC2HIP_ECAP);
+    if (d_payload && total > payload_stride) return set_err(c, VC2HIP_ECAP);
     CbrParams p;
     memset(&p, 0, sizeof p);
     p.store = d_store; p.store_stride = (long long)ns * g.slice_coefs; p.qidx = d_q; p.slice_bytes = d_cb;
@@ -1706,12 +1857,94 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
     p.n_bands = 3 * g.depth + 1;
     vc2_launch_cbr(c->L, p, n, c->stream);
   } else {
-    if (payload_stride < vc2hip_max_payload_bytes(f, cp)) return set_err(c, VC2HIP_ECAP);
+    if (d_payload && payload_stride < vc2hip_max_payload_bytes(f, cp)) return set_err(c, VC2HIP_ECAP);
     // quantIndicesConstQ, EncodeStream.cpp:128-138
     vc2_launch_fill_i32(c->L, d_q, cp->q_index, (size_t)n * ns, c->stream);
   }
-  return run_pack(c, g, n, d_store, d_q, qm, true, cp->prefix, cp->scalar, d_cb, d_co, total, (uint8_t *)d_payload,
-                  (long long)payload_stride, (unsigned long long *)d_lens, s16, d_storew);
+  if (d_payload && (rc = run_pack(c, g, n, d_store, d_q, qm, true, cp->prefix, cp->scalar, d_cb, d_co, total, (uint8_t *)d_payload,
+                                  (long long)payload_stride, (unsigned long long *)d_lens, s16, d_storew))) return rc;
+  return ro ? run_recon(c, g, cp, n, f, qm, s16, d_store, d_storew, d_q, ll, d_raw, *ro, d_cb, !d_payload, nullptr) : VC2HIP_OK;
+}
+
+// What follows the slice coder in vc2hip_encode_recon_batch_dev: the indices, the decoder's picture from the quantised
+// coefficients (no payload is read: DESIGN.md section 12), the squared error.  HQ: d_store holds transform coefficients,
+// which k_requantise turns into the decoder's store; LD: vc2_launch_ld_quantise left quantised values with LL residuals in
+// it, which is what the decoder's slice reader leaves.  check: no payload was written, the coder's checks are made here.
+static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f, const int32_t *qm,
+                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const void *d_raw, const ReconOut &ro,
+                     const int32_t *d_cb, bool check, const LdEncParams *ld) {
+  const int ns = g.ys * g.xs;
+  int rc;
+  if (ro.qidx) HIPCHK(c, hipMemcpyAsync(ro.qidx, d_q, (size_t)n * ns * 4, hipMemcpyDeviceToDevice, c->stream));
+  const void *dstc[3]; RawPlane ds[3];
+  raw_planes(f, ro.recon, 1, 1, dstc, ds);
+  void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
+  const bool plane_path = needs_plane_path(c, g, cp->kernel);
+  if (ld) {
+    if (check) vc2_launch_ld_check(c->L, *ld, n, c->stream);
+    if (ro.recon) {
+      LdLl3Params lp;
+      lp.store = d_store; lp.store_stride = (long long)ns * g.slice_coefs; lp.slice_coefs = g.slice_coefs;
+      lp.ys = g.ys; lp.xs = g.xs; lp.qidx = d_q; lp.qm0 = qm[0]; lp.err = c->d_err;
+      for (int k = 0; k < 3; ++k) {
+        lp.coef_off[k] = g.c[k].coef_off; lp.llh[k] = g.c[k].ph >> g.depth; lp.llw[k] = g.c[k].pw >> g.depth;
+        lp.ll_plane[k] = (int32_t *)ll.p[g.depth][k]; lp.ll_stride[k] = ll.stride[g.depth][k];
+      }
+      if (!vc2_launch_ld_ll3(c->L, lp, n, c->stream))
+        for (int k = 0; k < 3; ++k)
+          vc2_launch_ld_ll(c->L, d_store, (long long)ns * g.slice_coefs, g.slice_coefs, g.c[k].coef_off, g.c[k].n0,
+                           g.c[k].ph >> g.depth, g.c[k].pw >> g.depth, g.ys, g.xs, d_q, qm[0], (int32_t *)ll.p[g.depth][k],
+                           ll.stride[g.depth][k], n, c->d_err, c->stream);
+      if (plane_path) rc = plane_inverse(c, g, cp->kernel, n, d_store, d_q, qm, dst, ds, f, &ll);
+      else rc = run_inverse(c, g, cp->kernel, n, d_store, d_q, qm, true, true, ll, dst, ds, true, f);
+      if (rc) return rc;
+    }
+  } else if (ro.recon || check) {
+    // the decoder's layout, as decode_batch_common plans it for the same pictures (16-bit band planes: the byte form
+    // follows the statistics of a context's previous decode batch, which this call neither reads nor changes)
+    DecoderLayout lay;
+    plan_decoder_layout(c, g, cp->kernel, n, false, qm, dst, ds, f, s16, plane_path, lay);
+    int32_t *d_rs = nullptr, *d_rsw = nullptr;
+    if (ro.recon) {
+      NEED(c, B_RSTORE, (size_t)n * (size_t)lay.sstride * (s16 ? 2 : 4), d_rs);
+      if (s16) NEED(c, B_RSTOREW, (size_t)n * (size_t)lay.sstride * 4, d_rsw);
+    }
+    RequantParams p;
+    memset(&p, 0, sizeof p);
+    p.src = d_store; p.src_wide = d_storew; p.src_stride = (long long)ns * g.slice_coefs;
+    p.dst = d_rs; p.dst_wide = d_rsw; p.dst_stride = lay.sstride;
+    p.store16 = s16; p.qidx = d_q; p.n_slices = ns; p.slice_coefs = g.slice_coefs; p.xs = g.xs;
+    fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
+    p.n_bands = 3 * g.depth + 1;
+    for (int b = 0; b < p.n_bands; ++b) p.qmatrix[b] = qm[b];
+    p.bp = lay.bp; p.hs = lay.hs;
+    p.check = check; p.scalar = cp->scalar; p.cbr_bytes = d_cb; p.err = c->d_err;
+    vc2_launch_requantise(c->L, p, n, c->stream);
+    if (ro.recon) {
+      if (plane_path) rc = plane_inverse(c, g, cp->kernel, n, d_rs, d_q, qm, dst, ds, f);
+      else rc = run_inverse(c, g, cp->kernel, n, d_rs, d_q, qm, true, false, ll, dst, ds, true, f, s16, d_rsw, &lay.bp, lay.sstride, nullptr,
+                            lay.hs.n[0] ? &lay.hs : nullptr, lay.head_level);
+      if (rc) return rc;
+    }
+  }
+  if (ro.sse) {
+    HIPCHK(c, hipMemsetAsync(ro.sse, 0, (size_t)n * 3 * 8, c->stream));
+    vc2_prof_break(c->L);
+    SseParams p;
+    memset(&p, 0, sizeof p);
+    p.a = (const uint8_t *)d_raw; p.b = (const uint8_t *)ro.recon;
+    p.pic_bytes = (long long)vc2hip_raw_picture_bytes(f);
+    long long at = 0;
+    for (int k = 0; k < 3; ++k) {
+      p.comp_at[k] = at;
+      p.comp_bytes[k] = (long long)g.c[k].h * g.c[k].w * f->word_bytes;
+      at += p.comp_bytes[k];
+    }
+    p.word_bytes = f->word_bytes; p.shift = 8 * f->word_bytes - f->bit_depth;
+    p.sse = (unsigned long long *)ro.sse;
+    vc2_launch_squared_error(c->L, p, n, c->stream);
+  }
+  return VC2HIP_OK;
 }
 
 static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
@@ -1755,43 +1988,14 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   raw_planes(f, d_raw_out, fields, top_first, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
-  // Band planes (vc2hip_internal.h): the finest levels, as long as they go through the streaming inverse kernel, a
-  // slice's block row in them is at least 4 coefficients (8: rows that keep 16-byte pieces aligned) and they are not
-  // the level whose LL comes from the store.  16-bit store only (the int32 store is the fallback decoder's).
-  BandPlanes bp;
-  memset(&bp, 0, sizeof bp);
-  long long sstride = (long long)ns * g.slice_coefs; // elements per picture: slice records, then band planes
-  if (s16 && !plane_path && c->allow_planes) {
-    unsigned mask = 0;
-    LLPlanes none;
-    memset(&none, 0, sizeof none);
-    unsigned tails = 0;
-    (void)run_inverse(c, g, cp->kernel, n, nullptr, nullptr, qm, true, ld, none, dst, ds, true, f, s16, nullptr, nullptr, 0, &mask, nullptr, 1 << 30,
-                      nullptr, &tails);
-    for (int k = 0; k < 3; ++k) bp.from[k] = g.c[k].ph ? g.c[k].sh * g.c[k].sw : 0;
-    for (int l = 0; l < VC2_BP_MAX && l < g.depth - 1 && (mask >> l & 1); ++l) {
-      bool ok = true;
-      for (int k = 0; k < 3 && ok; ++k) {
-        const CompGeom &cg = g.c[k];
-        if (!cg.ph) continue;
-        const int bsh = (cg.sh >> l) / 2, bsw = (cg.sw >> l) / 2, ow = (cg.pw >> l) / 2;
-        ok = bsh >= 1 && bsw >= 4 && (bsh & (bsh - 1)) == 0 && (bsw & (bsw - 1)) == 0 && ow % (bsw >= 8 ? 8 : 4) == 0 &&
-             (bsh * bsw) % 8 == 0;
-      }
-      if (!ok) break;
-      for (int k = 0; k < 3; ++k) {
-        const CompGeom &cg = g.c[k];
-        if (!cg.ph) continue;
-        const int bsh = (cg.sh >> l) / 2, bsw = (cg.sw >> l) / 2;
-        bp.np[k][l] = (cg.ph >> l) / 2; bp.ow[k][l] = (cg.pw >> l) / 2;
-        bp.lbsh[k][l] = 31 - __builtin_clz(bsh); bp.lbsw[k][l] = 31 - __builtin_clz(bsw);
-        bp.base[k][l] = sstride;
-        sstride += ((long long)3 * bp.np[k][l] * bp.ow[k][l] + 7) & ~7ll;
-        bp.from[k] -= 3 * bsh * bsw;
-      }
-      bp.levels = l + 1;
-    }
-    if (sstride >= (1ll << 31)) { memset(&bp, 0, sizeof bp); sstride = (long long)ns * g.slice_coefs; } // 32-bit element offsets
+  DecoderLayout lay;
+  plan_decoder_layout(c, g, cp->kernel, n, ld, qm, dst, ds, f, s16, plane_path, lay);
+  BandPlanes &bp = lay.bp;
+  HeadSplit &hs = lay.hs;
+  const int head_level = lay.head_level;
+  long long sstride = lay.sstride;
+  const unsigned tails = lay.tails;
+  {
     // One byte per plane coefficient?  What the previous batch of this context looked like decides (its lengths and its
     // escape count arrive through pinned memory behind an event: no wait here): small coefficients <=> few payload bits per
     // sample.  The planes keep their places and their wide elements: only the bytes of a plane's narrow elements halve.
@@ -1819,35 +2023,6 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
       bool b8 = c->planes8_mode == 1 || (c->planes8_mode == 0 && c->planes8_on);
       for (int l = 0; l < bp.levels; ++l) if (tails >> l & 1) b8 = false; // (the TAIL instantiations read 16-bit planes only)
       bp.bytes8 = b8;
-    }
-  }
-  // Record heads (HeadSplit, vc2hip_internal.h): the levels below the streaming ones, when all of them run on the tile
-  // kernels, read their coefficients from dense per-component arrays behind the records (and band planes)
-  HeadSplit hs;
-  memset(&hs, 0, sizeof hs);
-  int head_level = 1 << 30;
-  if (s16 && !plane_path && c->allow_heads) {
-    unsigned smask = 0, fmask = 0;
-    LLPlanes none;
-    memset(&none, 0, sizeof none);
-    (void)run_inverse(c, g, cp->kernel, n, nullptr, nullptr, qm, true, ld, none, dst, ds, true, f, s16, nullptr, nullptr, 0, &smask, nullptr, 1 << 30, &fmask);
-    int ls = g.depth; // first level of the run of tile-kernel levels that reaches the deepest one
-    while (ls > 0 && !(smask >> (ls - 1) & 1) && (fmask >> (ls - 1) & 1)) --ls;
-    bool ok = ls >= 1 && ls < g.depth && ls >= bp.levels; // (level 0 keeps its bands where the final kernels expect them)
-    for (int k = 0; k < 3 && ok; ++k) {
-      if (!g.c[k].ph) continue;
-      const int hn = (g.c[k].sh >> ls) * (g.c[k].sw >> ls);
-      ok = hn >= 8 && hn % 8 == 0 && hn <= bp.from[k];
-    }
-    if (ok) {
-      long long at = sstride;
-      for (int k = 0; k < 3; ++k) {
-        if (!g.c[k].ph) continue;
-        hs.n[k] = (g.c[k].sh >> ls) * (g.c[k].sw >> ls);
-        hs.base[k] = at;
-        at += ((long long)ns * hs.n[k] + 7) & ~7ll;
-      }
-      if (at < (1ll << 31)) { sstride = at; head_level = ls; } else memset(&hs, 0, sizeof hs);
     }
   }
   int32_t *d_store, *d_ll, *d_q, *d_storew = nullptr, *d_llw = nullptr;

@@ -428,6 +428,45 @@ struct LdEncParams {
 void vc2_launch_ld_quantise(Launcher &L, const LdEncParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_ld_pack(Launcher &L, const LdEncParams &p, int n_pictures, hipStream_t s);
 
+// The picture the decoder will show, without a payload (vc2hip_recon.hip; vc2hip_encode_recon_batch_dev)
+// HQ: the encoder's slice records (transform coefficients) -> quantised values in the decoder's layout (slice records, band
+// planes, record heads: what the inverse level kernels read and dequantise).  16-bit elements on both sides, or int32 on both.
+struct RequantParams {
+  const void *src;            // the encoder's store: int16_t (store16) or int32_t elements
+  const int32_t *src_wide;
+  long long src_stride;       // per picture, elements
+  void *dst;                  // the decoder-layout store, same element type (null: the checks only)
+  int32_t *dst_wide;
+  long long dst_stride;
+  int store16;
+  const int32_t *qidx;        // n_pictures * n_slices
+  int n_slices, slice_coefs, xs;
+  int comp_n[3], comp_off[3], comp_n0[3];
+  int n_bands;
+  int qmatrix[VC2_MAX_BANDS];
+  BandPlanes bp;              // 16-bit planes only (bytes8 == 0)
+  HeadSplit hs;
+  // check != 0 (no payload was asked for): what the slice coder would have found -- a code beyond 32 bits, a component
+  // beyond 255 * scalar bytes, an HQ_CBR slice whose V component does not fit (k_hq_pack / k_hq_pack16: comp_len, cbr_v)
+  int check, scalar;
+  const int32_t *cbr_bytes;   // HQ_CBR: per slice budgets; null: VBR
+  unsigned *err;
+  int grp_log2;               // set by the launcher: log2 of the lanes that share a slice record
+};
+void vc2_upload_tables_recon(const QuantTables &t, hipStream_t s);
+void vc2_launch_requantise(Launcher &L, const RequantParams &p, int n_pictures, hipStream_t s);
+// LD without a payload: the checks of the slice writer (k_ld_pack) on the quantised store
+void vc2_launch_ld_check(Launcher &L, const LdEncParams &p, int n_pictures, hipStream_t s);
+// sums of squared sample differences of two raw buffers, per picture and component: sse[3 * pic + comp] += ...
+struct SseParams {
+  const uint8_t *a, *b;       // n pictures each, packed; both 16-byte aligned
+  long long pic_bytes;
+  long long comp_at[3], comp_bytes[3]; // a component's words inside a picture
+  int word_bytes, shift;      // sample = big-endian word >> shift
+  unsigned long long *sse;
+};
+void vc2_launch_squared_error(Launcher &L, const SseParams &p, int n_pictures, hipStream_t s);
+
 // VC-2 stream I/O (vc2hip_stream.hip)
 #define VC2_STREAM_HDR_MAX 48 // picture header bytes the write kernels carry (vc2hip_picture_header is far below it)
 struct StreamWriteParams {

@@ -3,6 +3,7 @@
 Plumbing only: every method is one C-ABI call; there is no Python or CPU implementation of
 the codec here, and construction fails loudly when the library or a GPU is missing."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -74,6 +75,7 @@ EXPORTS = [
     "vc2hip_decode_picture_begin", "vc2hip_decode_picture_end", "vc2hip_band_plane_bits", "vc2hip_dwt_launches",
     "vc2hip_picture_header", "vc2hip_stream_write_dev", "vc2hip_stream_read_dev",
     "vc2hip_encode_fields_batch_dev", "vc2hip_decode_fields_batch_dev", "vc2hip_decode_reduced_batch_dev",
+    "vc2hip_encode_recon_batch_dev",
 ]
 
 
@@ -136,6 +138,8 @@ def load_library():
                                                    C.POINTER(CodingParams), vp]
     lib.vc2hip_decode_reduced_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat),
                                                     C.POINTER(CodingParams), C.c_int, vp]
+    lib.vc2hip_encode_recon_batch_dev.argtypes = [vp, vp, C.c_int, C.POINTER(PictureFormat), C.POINTER(CodingParams),
+                                                  vp, C.c_size_t, vp, vp, vp, vp]
     lib.vc2hip_picture_header.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, u8p, C.c_size_t,
                                           C.POINTER(C.c_size_t)]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
@@ -182,6 +186,14 @@ def coding_params(lib, fmt, kernel, depth, u, a, mode="HQ_ConstQ", q=0, s=0, pre
     if not ys or not xs:
         raise ValueError("The given waveletDepth, hSlice, and vSlice parameters cannot encode this input.")
     return CodingParams(KERNELS[kernel], depth, ys, xs, MODES[mode], q, s, prefix, scalar)
+
+
+def psnr_db(sse, samples, bits):
+    """the figure EncodeStream -o PSNR prints for a sum of squared errors over `samples` samples of `bits` bits:
+    -20 log10(sqrt(sse / samples) / 2**bits), EncodeStream.cpp:716-717 (inf for sse == 0, as the reference's float division gives)"""
+    if sse == 0:
+        return float("inf")
+    return -20.0 * math.log10(math.sqrt(sse / samples) / float(1 << bits))
 
 
 def stream_params(major_version=2, first_picture_number=0, prev_parse_offset=0, end_of_sequence=False):
@@ -396,6 +408,12 @@ class Vc2Hip:
     def decode_reduced_batch_dev(self, d_payload, stride, d_lens, n, fmt, cp, drop_levels, d_raw_out):
         self._chk(self.lib.vc2hip_decode_reduced_batch_dev(self.h, d_payload, stride, d_lens, n, C.byref(fmt), C.byref(cp),
                                                            drop_levels, d_raw_out))
+
+    # the encode plus what it did to the pictures: d_recon (the decoder's pictures), d_sse (n x 3 uint64, needs d_recon), d_qidx
+    # (n x slices int32); d_payload / stride / d_lens all or none; any output may be None (vc2hip_encode_recon_batch_dev)
+    def encode_recon_batch_dev(self, d_raw, n, fmt, cp, d_payload=None, stride=0, d_lens=None, d_recon=None, d_sse=None, d_qidx=None):
+        self._chk(self.lib.vc2hip_encode_recon_batch_dev(self.h, d_raw, n, C.byref(fmt), C.byref(cp), d_payload, stride, d_lens,
+                                                         d_recon, d_sse, d_qidx))
 
     # interlaced frames as field pictures: frame_fmt is the frame's format, cp one field's; 2 * n_frames slots in stream order
     def encode_fields_batch_dev(self, d_frames, n_frames, frame_fmt, top_field_first, cp, d_payload, stride, d_lens):

@@ -74,6 +74,9 @@ int vc2hip_create(int device, vc2hip_ctx **out);
 int vc2hip_create_with_flags(int device, unsigned flags, vc2hip_ctx **out);
 /* same, but launch on a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) */
 int vc2hip_create_on_stream(int device, void *hip_stream, vc2hip_ctx **out);
+/* both: the caller's stream and the switches above (flags = 0: vc2hip_create_on_stream).  This is how a caller that captures
+ * graphs fixes the decoder's band-plane form: VC2HIP_FLAG_PLANES8_ALWAYS or _NEVER (see the batch calls below). */
+int vc2hip_create_on_stream_with_flags(int device, void *hip_stream, unsigned flags, vc2hip_ctx **out);
 void vc2hip_destroy(vc2hip_ctx *ctx);
 const char *vc2hip_last_error(const vc2hip_ctx *ctx);
 const char *vc2hip_error_string(int code);
@@ -238,9 +241,29 @@ int vc2hip_decode_picture_end(vc2hip_ctx *ctx, int ticket);
  * decoder's band planes (16-bit or byte elements: same results, different speed) follows the batch before; that batch's
  * payload lengths and escape count come back through pinned memory behind an event.  The context's SECOND decode call
  * waits for that event once (hipEventSynchronize: the first batch must have run); every later call only queries it.
- * On a caller's stream (vc2hip_create_on_stream) the call never waits, and while that stream is being captured into a
- * graph it records nothing.  Callers that need the same kernels launched whatever the host's timing (graph capture,
- * running far ahead of the GPU) create the context with VC2HIP_FLAG_PLANES8_ALWAYS or _NEVER. */
+ * On a caller's stream (vc2hip_create_on_stream / _on_stream_with_flags) the call never waits, and while that stream is being
+ * captured into a graph it records nothing and does not look at the batch before: the captured call has the form the context
+ * had when the capture began.  Callers that need the same kernels launched whatever the host's timing (graph capture,
+ * running far ahead of the GPU) create the context with vc2hip_create_on_stream_with_flags and VC2HIP_FLAG_PLANES8_ALWAYS
+ * or _NEVER.
+ *
+ * The contract on a caller's stream, for every batch and stream call of this header (tests/test_gpu_caller_stream.py):
+ *   - every launch, memset and copy of the call is enqueued on that stream (or on a vc2hip_set_streams lane forked from and
+ *     joined to it inside the call): work the caller enqueued on the stream before the call is complete before the call's
+ *     kernels run, work enqueued after it sees the call's results.  The host may run any number of calls ahead of the GPU.
+ *   - a call waits for the stream (hipStreamSynchronize) in exactly these cases: a workspace has to grow (the first sight
+ *     of a geometry or of a larger n, per lane); the per-slice budget table of HQ_CBR / LD pictures is not the one the context
+ *     holds (first sight, or a change of y_slices, x_slices, compressed_bytes, scalar or prefix: a context that alternates
+ *     HQ_CBR and LD pictures, or two budgets, uploads and waits at every change); the whole-plane inverse transform meets
+ *     another (wavelet, depth) than the one before.  Otherwise it allocates nothing, copies nothing to or from the host and
+ *     waits for nothing.  vc2hip_sync and vc2hip_set_streams always wait.
+ *   - graph capture: warm the context up first -- one eager call of every captured call, with the same fmt, cp and n, and
+ *     a vc2hip_sync -- so that none of the waits above falls inside the capture (there it fails: VC2HIP_EHIP, and the
+ *     capture is invalid).  A captured call returns VC2HIP_OK and leaves the context's host-side state as it was.  Errors
+ *     the kernels find in a replay surface at the next vc2hip_sync, as for an eager call.
+ *   - lanes (vc2hip_set_streams(k > 1)) under capture: supported, results identical.  The lanes become parallel branches of
+ *     the graph (fork and join events), and a lane follows the two rules above as the context itself does: no wait, and
+ *     nothing recorded while capturing. */
 /* Cut every device-resident batch into k contiguous sub-batches, each on its own HIP stream and workspace,
  * forked from and joined to the context's stream (k = 1: off, the default).  The launches of the sub-batches
  * overlap on the GPU; results are identical.  Extension, no counterpart in the reference. */

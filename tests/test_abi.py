@@ -60,6 +60,12 @@ def test_release_library_reads_no_environment():
                 assert any(depth), f"{os.path.basename(f)}:{n}: getenv outside a tools-only block: {t[:100]}"
 
 
+def test_the_callers_stream_constructor_with_flags_is_declared_and_bound():
+    import vc2hip_py
+    assert "vc2hip_create_on_stream_with_flags" in _declared()
+    assert "vc2hip_create_on_stream_with_flags" in vc2hip_py.EXPORTS
+
+
 def test_binding_covers_header():
     import vc2hip_py
     assert sorted(vc2hip_py.EXPORTS) == [n for n in _declared() if n in vc2hip_py.EXPORTS]

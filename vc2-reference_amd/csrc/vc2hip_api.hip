@@ -130,12 +130,18 @@ struct Buf {
 enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS, B_LENS, B_PAYLOAD,
        B_INDEX, B_PLANE, B_PLANE2, B_CBRB, B_CBRO, B_QM, B_UNITS, B_SEGS,
        B_RSTORE, B_RSTOREW, // encode_recon_batch_dev: the quantised coefficients in the decoder's layout
+       B_PLANE_QM,          // plane_inverse: the quantisation matrix of plane_qm_key
        B_COUNT };
 
 struct vc2hip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
+  // The context's work is ordered on a caller's stream: it was made by vc2hip_create_on_stream / _on_stream_with_flags, or it
+  // is a vc2hip_set_streams lane of such a context (a lane owns its stream, but the fork event pulls it into whatever the
+  // caller's stream is doing -- a graph capture included).  Such a context never waits for the GPU in a batch call and
+  // records nothing of its own while its stream is being captured (include/vc2hip.h).
+  bool follows_caller = false;
   unsigned *d_err = nullptr;
   unsigned *h_err = nullptr; // pinned: the first VC2_ERRBLK_COPY bytes of the error block
   Buf buf[B_COUNT];
@@ -144,6 +150,7 @@ struct vc2hip_ctx {
   // cached CBR / LD slice-size tables (re-uploaded only when the parameters change)
   int cbr_key[5] = {-1, -1, -1, -1, -1};
   uint64_t cbr_total = 0;
+  int plane_qm_key[2] = {-1, -1}; // (kernel, depth) of the quantisation matrix in B_PLANE_QM (whole-plane inverse path)
   int debug_skip = 0;
   // VBR payload assembly.  Default: fixed-stride slots + scan + compaction (three launches).
   // VC2HIP_SINGLE_PASS_VBR=1: decoupled look-back inside the pack kernel -- measured 2x SLOWER on
@@ -380,6 +387,7 @@ static int create_common(int device, hipStream_t stream, bool own, vc2hip_ctx **
   if (own) { if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { delete c; return VC2HIP_EHIP; } }
   c->stream = stream;
   c->own_stream = own;
+  c->follows_caller = !own;
   if (hipMalloc((void **)&c->d_err, 256 + 4096) != hipSuccess || // error word, then the LD search tables
      
       hipHostMalloc((void **)&c->h_err, VC2_ERRBLK_COPY) != hipSuccess ||
@@ -404,6 +412,9 @@ static int create_common(int device, hipStream_t stream, bool own, vc2hip_ctx **
 extern "C" int vc2hip_create(int device, vc2hip_ctx **out) { return create_common(device, nullptr, true, out); }
 extern "C" int vc2hip_create_with_flags(int device, unsigned flags, vc2hip_ctx **out) { return create_common(device, nullptr, true, out, flags); }
 extern "C" int vc2hip_create_on_stream(int device, void *s, vc2hip_ctx **out) { return create_common(device, (hipStream_t)s, false, out); }
+extern "C" int vc2hip_create_on_stream_with_flags(int device, void *s, unsigned flags, vc2hip_ctx **out) {
+  return create_common(device, (hipStream_t)s, false, out, flags);
+}
 extern "C" void vc2hip_destroy(vc2hip_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -489,6 +500,7 @@ extern "C" int vc2hip_set_streams(vc2hip_ctx *c, int k) {
       const int rc = vc2hip_create_with_flags(c->device, c->flags, &l);
       if (rc) return set_err(c, rc);
       l->L.on = c->L.on;
+      l->follows_caller = c->follows_caller;
     }
     c->lanes.push_back(l);
     hipEvent_t e;
@@ -508,6 +520,10 @@ extern "C" int vc2hip_set_streams(vc2hip_ctx *c, int k) {
 template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, F fn) {
   const int k = std::min<int>((int)c->lanes.size(), n);
   HIPCHK(c, hipSetDevice(c->device));
+  // A caller's stream was joined to every lane when the call before returned, and the fork event below follows that join:
+  // there is nothing left of the earlier sub-batches to wait for.  (Their join events may also have been recorded outside
+  // the graph capture this call is part of, or inside one that has ended: a wait on them here would not be a graph edge.)
+  if (!c->own_stream) for (vc2hip_ctx::LaneUse &u : c->lane_use) u.valid = false;
   HIPCHK(c, hipEventRecord(c->fork_ev, c->stream));
   std::vector<vc2hip_ctx::LaneUse> cur((size_t)c->lanes.size());
   std::vector<int> first((size_t)k), count((size_t)k);
@@ -1018,9 +1034,17 @@ static int plane_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, const 
   int32_t *d_plane;
   int *d_qm;
   NEED(c, B_PLANE, plane_elems(g) * n * 4, d_plane);
-  NEED(c, B_QM, 256, d_qm);
-  HIPCHK(c, hipMemcpyAsync(d_qm, qm, (size_t)(3 * g.depth + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // qm lives on the caller's stack
+  NEED(c, B_PLANE_QM, 256, d_qm);
+  // the matrix follows from (kernel, depth): uploaded when they change, as the CBR / LD budget tables are -- no copy and no
+  // wait in any later call.  (A reduced picture's matrix is the first 3 (depth - drop) + 1 entries of the CODED picture's:
+  // the key carries that depth, g.depth + level_base, beside the depth of the entries in use.)
+  const int key[2] = {kernel, g.depth | (g.depth + level_base) << 8};
+  if (memcmp(key, c->plane_qm_key, sizeof key)) {
+    c->plane_qm_key[0] = -1;
+    HIPCHK(c, hipMemcpyAsync(d_qm, qm, (size_t)(3 * g.depth + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // qm lives on the caller's stack
+    memcpy(c->plane_qm_key, key, sizeof key);
+  }
   const int ns = g.ys * g.xs;
   size_t off = 0;
   for (int k = 0; k < 3; ++k) {
@@ -1995,6 +2019,13 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   const int head_level = lay.head_level;
   long long sstride = lay.sstride;
   const unsigned tails = lay.tails;
+  // Is the stream being captured into a graph?  Asked of every context a caller's stream can pull into its capture: one
+  // made on that stream, and the lanes of one (their own streams join the capture at the fork event).
+  bool capturing = false;
+  if (c->follows_caller && !ld) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    capturing = hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  }
   {
     // One byte per plane coefficient?  What the previous batch of this context looked like decides (its lengths and its
     // escape count arrive through pinned memory behind an event: no wait here): small coefficients <=> few payload bits per
@@ -2004,9 +2035,11 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
       // anyway: a caller that never synchronises between batches would otherwise keep the 16-bit planes for as long as it
       // runs ahead of the GPU; every later look is only taken when it has arrived.  Never on a caller's stream
       // (vc2hip_create_on_stream): that caller may be capturing a graph or deliberately running ahead of the GPU -- there
-      // the look is only ever queried, and VC2HIP_FLAG_PLANES8_ALWAYS / _NEVER make the choice deterministic: include/vc2hip.h)
-      if (c->stat_pending && !c->stat_seen && c->own_stream) (void)hipEventSynchronize(c->stat_ev);
-      if (c->stat_pending && hipEventQuery(c->stat_ev) == hipSuccess) {
+      // the look is only ever queried, and VC2HIP_FLAG_PLANES8_ALWAYS / _NEVER make the choice deterministic: include/vc2hip.h.
+      // The lanes of such a context follow the same rule.  During a capture the look is not even queried: the form a
+      // captured call is planned with is the one the context had when the capture began)
+      if (c->stat_pending && !c->stat_seen && !c->follows_caller) (void)hipEventSynchronize(c->stat_ev);
+      if (c->stat_pending && !capturing && hipEventQuery(c->stat_ev) == hipSuccess) {
         c->stat_pending = false;
         c->stat_seen = true;
         double bytes = 0;
@@ -2071,13 +2104,8 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
     p.bp = bp; p.hs = hs; p.xs = g.xs;
     c->last_plane_bits = bp.levels ? (bp.bytes8 ? 8 : 16) : 0;
     p.stats = c->d_stat;
-    // (no look while the caller's stream is being captured into a graph: the copies and the event would become graph nodes
-    // and the event could never be queried)
-    bool capturing = false;
-    if (!c->own_stream) {
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      capturing = hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    }
+    // (no look while the stream is being captured into a graph: the copies and the event would become graph nodes and the
+    // event could never be queried)
     const bool track = bp.levels && c->planes8_mode == 0 && !c->stat_pending && !capturing;
     if (track) HIPCHK(c, hipMemsetAsync(c->d_stat, 0, 8, c->stream));
     vc2_launch_unpack(c->L, p, n, c->stream);

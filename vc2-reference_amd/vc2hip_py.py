@@ -62,7 +62,8 @@ class Vc2HipError(RuntimeError):
 
 
 EXPORTS = [
-    "vc2hip_create", "vc2hip_create_with_flags", "vc2hip_create_on_stream", "vc2hip_destroy", "vc2hip_last_error",
+    "vc2hip_create", "vc2hip_create_with_flags", "vc2hip_create_on_stream", "vc2hip_create_on_stream_with_flags", "vc2hip_destroy",
+    "vc2hip_last_error",
     "vc2hip_error_string", "vc2hip_sync", "vc2hip_padded_size", "vc2hip_slice_size_is_valid",
     "vc2hip_quant_matrix", "vc2hip_slice_bytes", "vc2hip_dwt_forward", "vc2hip_dwt_inverse",
     "vc2hip_quantise_np", "vc2hip_dequantise_np", "vc2hip_dequantise_ld", "vc2hip_hq_pack",
@@ -95,6 +96,7 @@ def load_library():
     lib.vc2hip_create.argtypes = [C.c_int, C.POINTER(vp)]
     lib.vc2hip_create_with_flags.argtypes = [C.c_int, C.c_uint, C.POINTER(vp)]
     lib.vc2hip_create_on_stream.argtypes = [C.c_int, vp, C.POINTER(vp)]
+    lib.vc2hip_create_on_stream_with_flags.argtypes = [C.c_int, vp, C.c_uint, C.POINTER(vp)]
     lib.vc2hip_destroy.argtypes = [vp]
     lib.vc2hip_destroy.restype = None
     lib.vc2hip_last_error.argtypes = [vp]
@@ -211,14 +213,15 @@ def picture_header(lib, cp, major_version, picture_number):
 
 
 class Vc2Hip:
-    """One context (= one GPU, one stream)."""
+    """One context (= one GPU, one stream).  stream: a caller-owned hipStream_t (e.g. torch.cuda.Stream().cuda_stream); flags:
+    a sum of FLAGS values; both may be given (vc2hip_create_on_stream_with_flags)."""
 
     def __init__(self, device=0, stream=None, flags=0):
         self.lib = load_library()
         h = C.c_void_p()
         if stream is not None and flags:
-            raise ValueError("vc2hip_create_on_stream takes no flags: give either a stream or flags")
-        if stream is None and flags:
+            rc = self.lib.vc2hip_create_on_stream_with_flags(device, C.c_void_p(stream), C.c_uint(flags), C.byref(h))
+        elif flags:
             rc = self.lib.vc2hip_create_with_flags(device, C.c_uint(flags), C.byref(h))
         elif stream is None:
             rc = self.lib.vc2hip_create(device, C.byref(h))

@@ -393,6 +393,48 @@ int vc2hip_picture_header(const vc2hip_coding_params *cp, int major_version, uin
 int vc2hip_stream_write_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
                             const vc2hip_coding_params *cp, const vc2hip_stream_params *sp,
                             uint8_t *d_stream, size_t cap, uint64_t *d_stream_len);
+/* Slots -> fragmented pictures (DataUnit.cpp:156-232 LD, :267-342 HQ; EncodeStream -F), then the end of sequence if asked
+ * for.  The slots and lengths are those of any batch call (after vc2hip_encode_fields_batch_dev: 2 n_frames pictures).
+ * Picture k, in order, is
+ *   the parameters fragment: parse info (code 0xEC HQ, 0xCC LD), picture number first_picture_number + k (mod 2^32, 4 bytes),
+ *       fragment data length (2 bytes: the length of the transform parameters), slice count 0 (2 bytes), the transform
+ *       parameters -- the bytes of vc2hip_picture_header after its first four, at sp->major_version;
+ *   slice fragments: parse info, picture number (4), data length (2), slice count (2), slice offset x (2) and y (2), then
+ *       that many whole slices in raster order.
+ * Grouping is the reference's greedy rule: a slice starts a new fragment when the current one holds at least one slice and
+ * adding this slice would make its bytes exceed fragment_length.  A larger slice travels alone, no fragment is empty, the
+ * last fragment is what remains.  Next and previous parse offsets are chained through every unit from sp->prev_parse_offset
+ * on; sp->end_of_sequence appends the 13-byte end unit.
+ * Slice boundaries: HQ_ConstQ and HQ_CBR from the payload itself (per slice: prefix bytes, the index byte, three times a
+ * length byte and length * scalar bytes); LD from the per-slice budget table of cp (vc2hip_slice_bytes(y_slices, x_slices,
+ * compressed_bytes, 1)).  HQ_ConstQ is an extension: the reference's EncodeStream refuses -F there, its Library does not.
+ *   *d_stream_len   the bytes the units need, even past cap; nothing is written at or past cap (VC2HIP_ECAP at sync)
+ *   d_unit_offsets, unit_cap, d_unit_count   all three, or NULL / 0 / NULL.  d_unit_offsets[i] = the byte offset of the i-th
+ *       data unit written, in stream order (the end of sequence is a unit); *d_unit_count = the number of units, even past
+ *       unit_cap; entries at or past unit_cap are not written (VC2HIP_ECAP at sync).  What a sender needs to hand the
+ *       fragments to a network stack without parsing the stream again.
+ * Worst case, to allocate by: at most y_slices * x_slices + 1 units per picture, plus one for the end of sequence; stream
+ * bytes at most sum of lens + n * (21 + parameter bytes) + n * y_slices * x_slices * 25 + 13 (the parameter bytes are
+ * vc2hip_picture_header's length - 4).
+ * VC2HIP_EINVAL, nothing launched, no output byte touched: sp->major_version < 3 (fragments exist from version 3 on, as
+ * DataUnit.cpp:1065-1067 forces it); fragment_length outside 1 ... 65535; x_slices or y_slices above 65535, or more than
+ * 2^24 slices; the unit-table arguments not all given or all absent; d_stream or the slots not 16-byte aligned, the other
+ * device pointers not 8-byte aligned; payload_stride of 4 GiB or more; everything vc2hip_stream_write_dev refuses.
+ * Found by the kernels, at vc2hip_sync: VC2HIP_ESTREAM for an HQ slot whose walk runs past d_lens[k] or does not end exactly
+ * on it, and for an LD slot whose length is not the table's sum; VC2HIP_ESYNTAX (the text names the limit) for a slice of
+ * more than 65535 bytes, which no fragment's 16-bit data length can carry (the reference truncates the field silently);
+ * VC2HIP_ECAP as above and for a d_lens[k] beyond payload_stride.  The stream bytes are unspecified after any of these;
+ * nothing outside [d_stream, d_stream + cap) or the unit table is ever written, and no slot byte past
+ * min(d_lens[k], payload_stride) is ever read.
+ * The stream calls' contract, word for word: asynchronous on the ctx stream, in order on a caller's stream; nothing allocated,
+ * copied to or from the host or waited for once the context has seen the geometry and n -- but for the LD budget table,
+ * under the rule stated for that table above; under graph capture, after a warm-up call, VC2HIP_OK and no host state
+ * changed.  No launch is sized by a read-back: the grids follow n, payload_stride and the slice count. */
+int vc2hip_stream_write_fragments_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride,
+                                      const uint64_t *d_lens, int n, const vc2hip_coding_params *cp,
+                                      const vc2hip_stream_params *sp, int fragment_length,
+                                      uint8_t *d_stream, size_t cap, uint64_t *d_stream_len,
+                                      uint64_t *d_unit_offsets, size_t unit_cap, uint64_t *d_unit_count);
 /* The first n pictures of a stream (len bytes at d_stream, any alignment) -> slots + lens, plus each picture's number and the
  * bytes consumed up to the end of the n-th picture (either may be NULL; a second call can resume at d_stream + consumed).
  * Sequence headers give the major version; padding and auxiliary units are skipped; whole pictures and fragmented pictures

@@ -129,6 +129,7 @@ struct Buf {
 };
 enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS, B_LENS, B_PAYLOAD,
        B_INDEX, B_PLANE, B_PLANE2, B_CBRB, B_CBRO, B_QM, B_UNITS, B_SEGS,
+       B_FRAGS, B_FRAGPIC, B_FRAGJUMP, // stream_write_fragments_dev: fragment tables, per-picture results, the cut's workspace
        B_RSTORE, B_RSTOREW, // encode_recon_batch_dev: the quantised coefficients in the decoder's layout
        B_PLANE_QM,          // plane_inverse: the quantisation matrix of plane_qm_key
        B_COUNT };
@@ -450,9 +451,14 @@ static int err_from_flags(vc2hip_ctx *c, unsigned f) {
                                              "picture parameters differ from the coding parameters",
                                              "custom quantisation matrix flag set", "asymmetric transform",
                                              "picture before any sequence header and no major version given",
-                                             "fragment out of order"};
+                                             "fragment out of order", "?"};
     const unsigned w = *(const unsigned *)((const char *)c->h_err + VC2_ERRBLK_SYNTAX_WHY);
     char b[256];
+    if (w == VC2_SYN_SLICE_TOO_LONG) {
+      snprintf(b, sizeof b, "picture %llu of the batch has a slice of more than 65535 bytes: a fragment's data length has 16 bits",
+               *(const unsigned long long *)((const char *)c->h_err + VC2_ERRBLK_SYNTAX_AT));
+      return set_err(c, VC2HIP_ESYNTAX, b);
+    }
     snprintf(b, sizeof b, "VC-2 stream syntax error at byte %llu: %s",
              *(const unsigned long long *)((const char *)c->h_err + VC2_ERRBLK_SYNTAX_AT), why[w < VC2_SYN_COUNT ? w : 0]);
     return set_err(c, VC2HIP_ESYNTAX, b);
@@ -2249,6 +2255,69 @@ extern "C" int vc2hip_stream_write_dev(vc2hip_ctx *c, const void *d_payload, siz
   p.first_picture_number = sp->first_picture_number; p.prev_parse_offset = sp->prev_parse_offset;
   vc2_launch_stream_layout(c->L, p, c->stream);
   vc2_launch_stream_copy(c->L, p, c->stream);
+  return VC2HIP_OK;
+}
+
+extern "C" int vc2hip_stream_write_fragments_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
+                                                 int n, const vc2hip_coding_params *cp, const vc2hip_stream_params *sp,
+                                                 int fragment_length, uint8_t *d_stream, size_t cap, uint64_t *d_stream_len,
+                                                 uint64_t *d_unit_offsets, size_t unit_cap, uint64_t *d_unit_count) {
+  if (!c || !d_payload || !d_lens || n < 1 || !cp || !sp || !d_stream || !d_stream_len) return set_err(c, VC2HIP_EINVAL);
+  if (((size_t)d_payload | payload_stride | (size_t)d_stream) & 15 ||
+      ((size_t)d_lens | (size_t)d_stream_len | (size_t)d_unit_offsets | (size_t)d_unit_count) & 7)
+    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  if (sp->major_version < 3) return set_err(c, VC2HIP_EINVAL, "fragments need major_version 3 or above");
+  if (fragment_length < 1 || fragment_length > 65535) return set_err(c, VC2HIP_EINVAL, "fragment_length must be 1 ... 65535");
+  if ((d_unit_offsets != nullptr) != (d_unit_count != nullptr) || (d_unit_offsets != nullptr) != (unit_cap != 0))
+    return set_err(c, VC2HIP_EINVAL, "d_unit_offsets, unit_cap and d_unit_count: all three or none");
+  if (!stream_cp_ok(cp) || cp->x_slices > 65535 || cp->y_slices > 65535 || (long long)cp->x_slices * cp->y_slices > (1 << 24))
+    return set_err(c, VC2HIP_EINVAL, "slice counts beyond a fragment's 16-bit slice offsets, or more than 2^24 slices");
+  if (payload_stride >= (1ull << 32)) return set_err(c, VC2HIP_EINVAL, "payload_stride must be below 4 GiB");
+  FragParams p;
+  memset(&p, 0, sizeof p);
+  uint8_t hdr[VC2_STREAM_HDR_MAX];
+  size_t hl = 0;
+  if (vc2hip_picture_header(cp, sp->major_version, 0, hdr, sizeof hdr, &hl) || hl < 4) return set_err(c, VC2HIP_EINVAL);
+  p.tp_len = (int)hl - 4; // the transform parameters: the header without its picture number
+  memcpy(p.tp, hdr + 4, (size_t)p.tp_len);
+  ENTER(c);
+  const int ns = cp->y_slices * cp->x_slices;
+  int rc;
+  p.hq = cp->mode != VC2HIP_LD;
+  if (p.hq) {
+    uint32_t *d_offs;
+    if ((rc = build_index(c, (const uint8_t *)d_payload, (long long)payload_stride, (const unsigned long long *)d_lens, n, ns,
+                          cp->prefix, cp->scalar, &d_offs))) return rc;
+    p.offs = d_offs; p.offs_stride = ns;
+  } else { // the per-slice budget table the LD coder uses (vc2hip_encode_batch_dev / decode_batch_dev)
+    const int key[5] = {cp->y_slices, cp->x_slices, cp->compressed_bytes, 1, -7};
+    if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
+      std::vector<int32_t> sb(ns);
+      int32_t *d_sb; uint32_t *d_so; uint64_t total;
+      vc2hip_slice_bytes(cp->y_slices, cp->x_slices, cp->compressed_bytes, 1, sb.data());
+      if ((rc = ld_offsets_upload(c, sb.data(), ns, &d_sb, &d_so, &total))) return rc;
+      memcpy(c->cbr_key, key, sizeof key);
+      c->cbr_total = total;
+    }
+    p.offs = (const uint32_t *)c->buf[B_CBRO].p; p.offs_stride = 0; p.ld_total = c->cbr_total;
+  }
+  NEED(c, B_FRAGS, (size_t)n * ns * sizeof(uint4), p.table);
+  char *pic;
+  NEED(c, B_FRAGPIC, (size_t)n * 32, pic);
+  p.meta = (uint4 *)pic; p.pic_base = (unsigned long long *)(pic + (size_t)n * 16); p.unit_base = p.pic_base + n;
+  if (!vc2_frag_cut_lds(ns)) NEED(c, B_FRAGJUMP, (size_t)n * vc2_frag_jump_bytes(ns), p.jump);
+  p.payload = (const uint8_t *)d_payload; p.payload_stride = (long long)payload_stride;
+  p.lens = (const unsigned long long *)d_lens;
+  p.prefix = cp->prefix; p.scalar = cp->scalar;
+  p.n = n; p.ns = ns; p.xs = cp->x_slices; p.fragment_length = (unsigned)fragment_length;
+  p.stream = d_stream; p.cap = cap; p.stream_len = (unsigned long long *)d_stream_len;
+  p.unit_offsets = (unsigned long long *)d_unit_offsets; p.unit_cap = unit_cap; p.unit_count = (unsigned long long *)d_unit_count;
+  p.err = c->d_err;
+  p.code = p.hq ? 0xEC : 0xCC; p.eos = sp->end_of_sequence != 0;
+  p.first_picture_number = sp->first_picture_number; p.prev_parse_offset = sp->prev_parse_offset;
+  vc2_launch_frag_cut(c->L, p, c->stream);
+  vc2_launch_frag_layout(c->L, p, c->stream);
+  vc2_launch_frag_copy(c->L, p, c->stream);
   return VC2HIP_OK;
 }
 

@@ -38,7 +38,9 @@ enum : unsigned {
 #define VC2_ERRBLK_COPY 32          // bytes vc2hip_sync copies back
 enum {
   VC2_SYN_PREFIX = 1, VC2_SYN_CODE, VC2_SYN_PAST_END, VC2_SYN_NEXT_ZERO, VC2_SYN_FEWER, VC2_SYN_PARAMS, VC2_SYN_QUANT_MATRIX,
-  VC2_SYN_ASYMMETRIC, VC2_SYN_NO_VERSION, VC2_SYN_FRAGMENT, VC2_SYN_COUNT
+  VC2_SYN_ASYMMETRIC, VC2_SYN_NO_VERSION, VC2_SYN_FRAGMENT,
+  VC2_SYN_SLICE_TOO_LONG, // fragment writer: a slice of more than 65535 bytes (VC2_ERRBLK_SYNTAX_AT holds the picture's index)
+  VC2_SYN_COUNT
 };
 
 struct CompGeom {
@@ -499,6 +501,39 @@ struct StreamReadParams {
   unsigned long long *consumed;     // may be null
   unsigned *err;
 };
+// fragmented pictures (vc2hip_stream_write_fragments_dev)
+#define VC2_FRAG_HEADER 25 // parse info, picture number, data length, slice count, slice offset x and y
+struct FragParams {
+  const uint8_t *payload;           // slots
+  long long payload_stride;
+  const unsigned long long *lens;   // n payload lengths
+  const uint32_t *offs;             // slice start bytes: HQ offs[k * ns + i] (the decoder's slice index), LD offs[i] (the budget table's)
+  long long offs_stride;            // ns (HQ) or 0 (LD)
+  unsigned long long ld_total;      // LD: the table's sum
+  int hq, prefix, scalar;
+  int n, ns, xs;
+  unsigned fragment_length;
+  uint4 *table;                     // workspace: n * ns fragments {first slice, first payload byte, bytes, slices}
+  uint4 *meta;                      // workspace: per picture {slice fragments, payload bytes, bytes of the last fragment, 0}
+  unsigned long long *pic_base;     // workspace: n stream offsets of the pictures' parameters fragments
+  unsigned long long *unit_base;    // workspace: n indices of those units in the stream
+  unsigned *jump;                   // workspace of the cut when a picture's slices do not fit LDS, else null
+  uint8_t *stream;
+  unsigned long long cap;
+  unsigned long long *stream_len;
+  unsigned long long *unit_offsets; // may be null
+  unsigned long long unit_cap;
+  unsigned long long *unit_count;   // may be null
+  unsigned *err;
+  int code, eos, tp_len;
+  uint32_t first_picture_number, prev_parse_offset;
+  uint8_t tp[VC2_STREAM_HDR_MAX];   // transform parameters
+};
+size_t vc2_frag_cut_lds(int ns);        // dynamic LDS of the cut, 0: the slices do not fit (FragParams::jump)
+size_t vc2_frag_jump_bytes(int ns);     // that workspace, per picture
+void vc2_launch_frag_cut(Launcher &L, const FragParams &p, hipStream_t s);
+void vc2_launch_frag_layout(Launcher &L, const FragParams &p, hipStream_t s);
+void vc2_launch_frag_copy(Launcher &L, const FragParams &p, hipStream_t s);
 void vc2_launch_stream_layout(Launcher &L, const StreamWriteParams &p, hipStream_t s);
 void vc2_launch_stream_copy(Launcher &L, const StreamWriteParams &p, hipStream_t s);
 void vc2_launch_stream_walk(Launcher &L, const StreamReadParams &p, hipStream_t s);

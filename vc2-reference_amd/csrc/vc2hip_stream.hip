@@ -3,6 +3,9 @@
 //
 //   write: k_stream_layout (one workgroup: unit offsets by a scan of the payload lengths, parse infos, picture headers, end of
 //          sequence) -> k_stream_copy (pictures x chunks: every slot to its unit, realigned in registers)
+//   write, fragmented: the decoder's slice index (HQ; LD takes the budget table) -> k_frag_cut (a workgroup per picture: the
+//          greedy cut by binary search and pointer jumping) -> k_frag_layout + k_frag_headers (scan over pictures, parse infos
+//          and fragment headers) -> k_frag_copy (pictures x chunks of the stream: every fragment's slices, realigned in registers)
 //   read:  k_stream_walk (one wavefront: follows the parse-info chain, checks every picture's parameters, lists each picture's
 //          payload segments) -> k_stream_gather (pictures x chunks: the segments into the slots, realigned in registers)
 //
@@ -41,11 +44,11 @@ __device__ __forceinline__ unsigned long long vc2_unit_bytes(const StreamWritePa
   const unsigned long long l = p.lens[k];
   return 13ull + (unsigned)p.hdr_len + (l < (unsigned long long)p.payload_stride ? l : (unsigned long long)p.payload_stride);
 }
-__device__ __forceinline__ void vc2_put(const StreamWriteParams &p, unsigned long long at, unsigned v) {
+template <typename P> __device__ __forceinline__ void vc2_put(const P &p, unsigned long long at, unsigned v) {
   if (at < p.cap) p.stream[at] = (uint8_t)v;
 }
-__device__ void vc2_put_parse_info(const StreamWriteParams &p, unsigned long long at, int code, unsigned long long next,
-                                   unsigned long long prev) {
+template <typename P>
+__device__ void vc2_put_parse_info(const P &p, unsigned long long at, int code, unsigned long long next, unsigned long long prev) {
   const unsigned head[5] = {0x42, 0x42, 0x43, 0x44, (unsigned)code};
   for (int i = 0; i < 5; ++i) vc2_put(p, at + i, head[i]);
   for (int i = 0; i < 4; ++i) {
@@ -132,6 +135,303 @@ void vc2_launch_stream_copy(Launcher &L, const StreamWriteParams &p, hipStream_t
   const int chunks = (int)(((unsigned long long)p.payload_stride / 16 + 2 + VC2_COPY_CHUNK - 1) / VC2_COPY_CHUNK);
   vc2_prof_begin(L, "stream_copy", s);
   VC2_LAUNCH(L, k_stream_copy, dim3((unsigned)(chunks * p.n)), dim3(VC2_COPY_THREADS), 0, s, p, chunks);
+  vc2_prof_end(L, s);
+}
+
+// ------------------------------------------------------------------------------------------
+// write, fragmented (DataUnit.cpp:156-232, :267-342)
+// ------------------------------------------------------------------------------------------
+#define VC2_CUT_THREADS 1024
+#define VC2_FRAG_STAGE (16 * VC2_COPY_CHUNK / VC2_FRAG_HEADER + 2) // fragments a chunk of k_frag_copy can meet
+#define VC2_CUT_LDS_MAX (144u << 10) // dynamic LDS of k_frag_cut (it holds 4 KiB more statically; a workgroup has 160 KiB)
+
+// marks (one bit per slice) and two arrays of ns + 1 jump targets: 16-bit in LDS, 32-bit in the workspace
+static size_t frag_words(int ns) { return ((size_t)ns + 31) >> 5; }
+size_t vc2_frag_cut_lds(int ns) {
+  const size_t b = frag_words(ns) * 4 + ((((size_t)ns + 1) * 2 * 2 + 3) & ~(size_t)3);
+  return ns <= 65535 && b <= VC2_CUT_LDS_MAX ? b : 0;
+}
+size_t vc2_frag_jump_bytes(int ns) { return (frag_words(ns) + ((size_t)ns + 1) * 2) * 4; }
+
+__device__ __forceinline__ unsigned vc2_frag_p0(const FragParams &p) { return 21u + (unsigned)p.tp_len; } // the parameters fragment
+__device__ __forceinline__ unsigned long long vc2_frag_pic_bytes(const FragParams &p, uint4 m) {
+  return vc2_frag_p0(p) + (unsigned long long)VC2_FRAG_HEADER * m.x + m.y;
+}
+__device__ __forceinline__ unsigned vc2_frag_last_unit(const FragParams &p, uint4 m) { // bytes of a picture's last data unit
+  return m.x ? VC2_FRAG_HEADER + m.z : vc2_frag_p0(p);
+}
+
+// One workgroup per picture.  Slice i starts at payload byte O(i), O(ns) = the payload's length.  A fragment that starts at
+// slice i ends before nxt(i) = the largest j with O(j) - O(i) <= fragment_length, or i + 1 (a slice beyond the length travels
+// alone): a binary search per slice.  The fragments of the picture are the chain 0, nxt(0), nxt(nxt(0)), ...; it is marked
+// by pointer jumping -- round r marks the a[i] of every marked i and squares a -- which ends when a round marks nothing new
+// (the marked set is then closed under a = nxt^(2^r) and holds the chain's first 2^r elements: all of it).  A slice marked
+// early by a thread that saw this round's marks is still one of the chain.  The marked slices, counted in order, are the table.
+template <typename J> __global__ __launch_bounds__(VC2_CUT_THREADS) void k_frag_cut(FragParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned cut_lds[];
+  __shared__ unsigned part[VC2_CUT_THREADS];
+  __shared__ unsigned long long total_s;
+  __shared__ int bad_s, changed_s;
+  constexpr int T = VC2_CUT_THREADS;
+  const int k = blockIdx.x, t = threadIdx.x, ns = p.ns;
+  const unsigned words = (unsigned)(ns + 31) >> 5;
+  unsigned *marks = p.jump ? p.jump + (size_t)k * (words + 2 * ((size_t)ns + 1)) : cut_lds;
+  J *a = (J *)(marks + words), *b = a + (ns + 1);
+  const unsigned long long len = p.lens[k], stride = (unsigned long long)p.payload_stride, plen = len < stride ? len : stride;
+  const uint32_t *offs = p.offs + (long long)k * p.offs_stride;
+  const uint8_t *slot = p.payload + (long long)k * p.payload_stride;
+  if (t == 0) {
+    unsigned long long total = p.ld_total;
+    bool ok = true;
+    if (p.hq) { // the end of the last slice, from its three length bytes
+      unsigned long long q = offs[ns - 1];
+      ok = offs[0] == 0 && q < plen;
+      q += (unsigned)p.prefix + 1;
+      for (int c = 0; c < 3 && ok; ++c) {
+        ok = q < plen;
+        if (ok) q += 1 + (unsigned long long)slot[q] * (unsigned)p.scalar;
+      }
+      total = q;
+    }
+    total_s = total;
+    bad_s = !ok || total != len || len > stride;
+    changed_s = 0;
+  }
+  __syncthreads();
+  if (p.hq) { // the index's offsets ascend (an unreached slice holds 0xFFFFFFFF)
+    bool bad = false;
+    for (int i = t; i + 1 < ns; i += T) bad |= offs[i] >= offs[i + 1];
+    if (bad) bad_s = 1;
+  }
+  __syncthreads();
+  const unsigned long long total = total_s;
+  if (bad_s) { // (uniform) no slice fragment is written for this picture
+    if (t == 0) {
+      p.meta[k] = make_uint4(0, 0, 0, 0);
+      atomicOr(p.err, len > stride ? VC2_DEVERR_CAP : VC2_DEVERR_STREAM);
+    }
+    return;
+  }
+  const unsigned long long F = p.fragment_length;
+  for (int i = t; i < ns; i += T) {
+    const unsigned long long o = offs[i];
+    int lo = i + 1, hi = ns;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if ((mid < ns ? (unsigned long long)offs[mid] : total) - o <= F) lo = mid; else hi = mid - 1;
+    }
+    a[i] = (J)lo;
+  }
+  if (t == 0) a[ns] = (J)ns;
+  for (unsigned w = t; w < words; w += T) marks[w] = w == 0 ? 1u : 0u;
+  __syncthreads();
+  for (;;) {
+    bool ch = false;
+    for (int i = t; i < ns; i += T) {
+      if (!(marks[i >> 5] >> (i & 31) & 1)) continue;
+      const int j = (int)a[i];
+      if (j < ns && !(marks[j >> 5] >> (j & 31) & 1)) { atomicOr(&marks[j >> 5], 1u << (j & 31)); ch = true; }
+    }
+    if (ch) changed_s = 1;
+    __syncthreads();
+    const int c = changed_s;
+    __syncthreads();
+    if (!c) break;
+    if (t == 0) changed_s = 0;
+    for (int i = t; i <= ns; i += T) b[i] = a[a[i]];
+    __syncthreads();
+    J *x = a; a = b; b = x;
+  }
+  // the marked slices in order: b[f] = the first slice of fragment f
+  const unsigned per = (words + T - 1) / T, w0 = min(words, t * per), w1 = min(words, w0 + per);
+  unsigned cnt = 0;
+  for (unsigned w = w0; w < w1; ++w) cnt += __popc(marks[w]);
+  part[t] = cnt;
+  __syncthreads();
+  for (int off = 1; off < T; off <<= 1) {
+    const unsigned v = t >= off ? part[t - off] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  unsigned f = part[t] - cnt;
+  const unsigned nfrag = part[T - 1];
+  for (unsigned w = w0; w < w1; ++w)
+    for (unsigned m = marks[w]; m; m &= m - 1) b[f++] = (J)(w * 32 + (__ffs(m) - 1));
+  __syncthreads();
+  for (f = t; f < nfrag; f += T) {
+    const int i = (int)b[f], j = f + 1 < nfrag ? (int)b[f + 1] : ns;
+    const unsigned long long o = offs[i], l = (j < ns ? (unsigned long long)offs[j] : total) - o;
+    p.table[(size_t)k * ns + f] = make_uint4((unsigned)i, (unsigned)o, (unsigned)l, (unsigned)(j - i));
+    if (f == nfrag - 1) p.meta[k] = make_uint4(nfrag, (unsigned)total, (unsigned)l, 0);
+    if (l > 65535) { // one slice (several share a fragment only within fragment_length): the 16-bit data length cannot hold it
+      *(unsigned long long *)((char *)p.err + VC2_ERRBLK_SYNTAX_AT) = (unsigned long long)k;
+      *(unsigned *)((char *)p.err + VC2_ERRBLK_SYNTAX_WHY) = (unsigned)VC2_SYN_SLICE_TOO_LONG;
+      __threadfence();
+      atomicOr(p.err, VC2_DEVERR_SYNTAX);
+    }
+  }
+}
+
+// one workgroup: the pictures' stream offsets and unit indices by a scan, their parameters fragments, the end of sequence
+__global__ __launch_bounds__(VC2_SCAN_THREADS) void k_frag_layout(FragParams p) {
+  __shared__ unsigned long long part[VC2_SCAN_THREADS], upart[VC2_SCAN_THREADS];
+  const int t = threadIdx.x;
+  const int per = (p.n + VC2_SCAN_THREADS - 1) / VC2_SCAN_THREADS;
+  const int k0 = min(p.n, t * per), k1 = min(p.n, k0 + per);
+  const unsigned p0 = vc2_frag_p0(p);
+  unsigned long long sum = 0, usum = 0;
+  for (int k = k0; k < k1; ++k) {
+    const uint4 m = p.meta[k];
+    sum += vc2_frag_pic_bytes(p, m);
+    usum += 1ull + m.x;
+  }
+  part[t] = sum;
+  upart[t] = usum;
+  __syncthreads();
+  for (int off = 1; off < VC2_SCAN_THREADS; off <<= 1) {
+    const unsigned long long v = t >= off ? part[t - off] : 0, u = t >= off ? upart[t - off] : 0;
+    __syncthreads();
+    part[t] += v;
+    upart[t] += u;
+    __syncthreads();
+  }
+  unsigned long long at = part[t] - sum, unit = upart[t] - usum;
+  for (int k = k0; k < k1; ++k) {
+    const uint4 m = p.meta[k];
+    p.pic_base[k] = at;
+    p.unit_base[k] = unit;
+    if (p.unit_offsets && unit < p.unit_cap) p.unit_offsets[unit] = at;
+    vc2_put_parse_info(p, at, p.code, p0, k ? vc2_frag_last_unit(p, p.meta[k - 1]) : p.prev_parse_offset);
+    const uint32_t pn = p.first_picture_number + (uint32_t)k;
+    for (int i = 0; i < 4; ++i) vc2_put(p, at + 13 + i, pn >> (24 - 8 * i));
+    vc2_put(p, at + 17, (unsigned)p.tp_len >> 8);
+    vc2_put(p, at + 18, (unsigned)p.tp_len);
+    vc2_put(p, at + 19, 0);
+    vc2_put(p, at + 20, 0);
+    for (int i = 0; i < p.tp_len; ++i) vc2_put(p, at + 21 + i, p.tp[i]);
+    at += vc2_frag_pic_bytes(p, m);
+    unit += 1ull + m.x;
+  }
+  if (t == 0) {
+    const unsigned long long total = part[VC2_SCAN_THREADS - 1], units = upart[VC2_SCAN_THREADS - 1];
+    if (p.eos) {
+      vc2_put_parse_info(p, total, 0x10, 0, vc2_frag_last_unit(p, p.meta[p.n - 1]));
+      if (p.unit_offsets && units < p.unit_cap) p.unit_offsets[units] = total;
+    }
+    const unsigned long long end = total + (p.eos ? 13 : 0), count = units + (p.eos ? 1 : 0);
+    *p.stream_len = end;
+    if (p.unit_count) *p.unit_count = count;
+    if (end > p.cap || (p.unit_offsets && count > p.unit_cap)) atomicOr(p.err, VC2_DEVERR_CAP);
+  }
+}
+
+// grid: (fragments / 256, pictures): one thread writes one slice fragment's parse info and header
+__global__ __launch_bounds__(256) void k_frag_headers(FragParams p) {
+  const int k = blockIdx.y;
+  const unsigned f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= p.meta[k].x) return;
+  const uint4 *tab = p.table + (size_t)k * p.ns;
+  const uint4 g = tab[f];
+  const unsigned p0 = vc2_frag_p0(p);
+  const unsigned long long at = p.pic_base[k] + p0 + (unsigned long long)VC2_FRAG_HEADER * f + g.y, unit = p.unit_base[k] + 1 + f;
+  if (p.unit_offsets && unit < p.unit_cap) p.unit_offsets[unit] = at;
+  vc2_put_parse_info(p, at, p.code, (unsigned long long)VC2_FRAG_HEADER + g.z, f ? VC2_FRAG_HEADER + tab[f - 1].z : p0);
+  const uint32_t pn = p.first_picture_number + (uint32_t)k;
+  for (int i = 0; i < 4; ++i) vc2_put(p, at + 13 + i, pn >> (24 - 8 * i));
+  const unsigned field[4] = {g.z, g.w, g.x % (unsigned)p.xs, g.x / (unsigned)p.xs}; // data length, slices, slice offset x, y
+  for (int i = 0; i < 4; ++i) {
+    vc2_put(p, at + 17 + 2 * i, field[i] >> 8);
+    vc2_put(p, at + 18 + 2 * i, field[i]);
+  }
+}
+
+// grid: pictures x chunks of VC2_COPY_CHUNK aligned 16-byte words of the stream, from the picture's first slice fragment on.
+// The fragments start at ascending stream offsets: the workgroup finds those its chunk meets, every word its own among them.
+__global__ __launch_bounds__(VC2_COPY_THREADS) void k_frag_copy(FragParams p, int chunks) {
+  const int k = blockIdx.x / chunks, chunk = blockIdx.x - k * chunks;
+  const uint4 m = p.meta[k];
+  const int nfrag = (int)m.x;
+  if (!nfrag) return;
+  const uint4 *tab = p.table + (size_t)k * p.ns;
+  const unsigned long long plen = m.y; // (the cut has checked it against the slot)
+  const unsigned long long unit0 = p.pic_base[k] + vc2_frag_p0(p); // fragment f's unit is at unit0 + 25 f + tab[f].y
+  const unsigned long long all = unit0 + (unsigned long long)VC2_FRAG_HEADER * nfrag + plen, end = all < p.cap ? all : p.cap;
+  if (unit0 >= end) return;
+  const unsigned long long b1 = (end + 15) >> 4, c0 = (unit0 >> 4) + (unsigned long long)chunk * VC2_COPY_CHUNK;
+  if (c0 >= b1) return;
+  auto find = [&](unsigned long long x, int lo, int hi) { // the last fragment of [lo, hi] whose unit starts at or before x (else lo)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (unit0 + (unsigned long long)VC2_FRAG_HEADER * mid + tab[mid].y <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+  };
+  // the fragments this chunk meets, staged in LDS: their units start at least a header apart, so there are at most
+  // VC2_FRAG_STAGE of them; every word then finds its own among them
+  __shared__ unsigned long long key_s[VC2_FRAG_STAGE];
+  __shared__ uint4 ent_s[VC2_FRAG_STAGE];
+  const int fa = find(c0 << 4, 0, nfrag - 1), fb = find(((c0 + VC2_COPY_CHUNK) << 4) - 1, fa, nfrag - 1);
+  const int cnt = min(fb - fa + 1, VC2_FRAG_STAGE);
+  for (int i = threadIdx.x; i < cnt; i += VC2_COPY_THREADS) {
+    const uint4 g = tab[fa + i];
+    ent_s[i] = g;
+    key_s[i] = unit0 + (unsigned long long)VC2_FRAG_HEADER * (fa + i) + g.y;
+  }
+  __syncthreads();
+  const uint8_t *slot8 = p.payload + (long long)k * p.payload_stride;
+#pragma unroll
+  for (int i = 0; i < VC2_COPY_WORDS; ++i) {
+    const unsigned long long b = c0 + i * VC2_COPY_THREADS + threadIdx.x;
+    if (b >= b1) break;
+    const unsigned long long x0 = b << 4;
+    int lo = 0, hi = cnt - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (key_s[mid] <= x0) lo = mid; else hi = mid - 1;
+    }
+    const int f = fa + lo;
+    const uint4 g = ent_s[lo];
+    // the body of fragment f: stream bytes [s0, s1) are slot bytes [g.y, g.y + g.z).  No later body begins in this word (a
+    // header is longer than a word); the headers are k_frag_headers'
+    const unsigned long long s0 = unit0 + (unsigned long long)VC2_FRAG_HEADER * (f + 1) + g.y, s1 = s0 + g.z;
+    const unsigned long long src = g.y + (x0 - s0);
+    const unsigned r = (unsigned)(src & 15);
+    // whole words of the slot (it is 16-byte aligned) that end inside the payload; every other word goes byte by byte
+    if (x0 >= s0 && x0 + 16 <= s1 && x0 + 16 <= end && src - r + (r ? 32 : 16) <= plen) {
+      const uint4 *w = (const uint4 *)(slot8 + (src - r));
+      *(uint4 *)(p.stream + x0) = r ? vc2_realign(w[0], w[1], r) : w[0];
+    } else {
+      for (int e = 0; e < 16; ++e) {
+        const unsigned long long x = x0 + e;
+        if (x >= s0 && x < s1 && x < end) p.stream[x] = slot8[g.y + (x - s0)];
+      }
+    }
+  }
+}
+
+void vc2_launch_frag_cut(Launcher &L, const FragParams &p, hipStream_t s) {
+  const size_t lds = p.jump ? 0 : vc2_frag_cut_lds(p.ns);
+  vc2_prof_begin(L, "frag_cut", s);
+  if (p.jump) VC2_LAUNCH(L, k_frag_cut<unsigned>, dim3((unsigned)p.n), dim3(VC2_CUT_THREADS), 0, s, p);
+  else {
+    vc2_allow_lds((const void *)k_frag_cut<unsigned short>, lds);
+    VC2_LAUNCH(L, k_frag_cut<unsigned short>, dim3((unsigned)p.n), dim3(VC2_CUT_THREADS), lds, s, p);
+  }
+  vc2_prof_end(L, s);
+}
+void vc2_launch_frag_layout(Launcher &L, const FragParams &p, hipStream_t s) {
+  vc2_prof_begin(L, "frag_layout", s);
+  VC2_LAUNCH(L, k_frag_layout, dim3(1), dim3(VC2_SCAN_THREADS), 0, s, p);
+  VC2_LAUNCH(L, k_frag_headers, dim3((unsigned)((p.ns + 255) / 256), (unsigned)p.n), dim3(256), 0, s, p);
+  vc2_prof_end(L, s);
+}
+void vc2_launch_frag_copy(Launcher &L, const FragParams &p, hipStream_t s) {
+  // a picture's slice fragments are at most stride + 25 ns bytes of the stream
+  const unsigned long long words = ((unsigned long long)p.payload_stride + (unsigned long long)VC2_FRAG_HEADER * p.ns) / 16 + 2;
+  const int chunks = (int)((words + VC2_COPY_CHUNK - 1) / VC2_COPY_CHUNK);
+  vc2_prof_begin(L, "frag_copy", s);
+  VC2_LAUNCH(L, k_frag_copy, dim3((unsigned)(chunks * p.n)), dim3(VC2_COPY_THREADS), 0, s, p, chunks);
   vc2_prof_end(L, s);
 }
 

@@ -76,7 +76,7 @@ EXPORTS = [
     "vc2hip_decode_picture_begin", "vc2hip_decode_picture_end", "vc2hip_band_plane_bits", "vc2hip_dwt_launches",
     "vc2hip_picture_header", "vc2hip_stream_write_dev", "vc2hip_stream_read_dev",
     "vc2hip_encode_fields_batch_dev", "vc2hip_decode_fields_batch_dev", "vc2hip_decode_reduced_batch_dev",
-    "vc2hip_encode_recon_batch_dev",
+    "vc2hip_encode_recon_batch_dev", "vc2hip_stream_write_fragments_dev",
 ]
 
 
@@ -146,6 +146,8 @@ def load_library():
                                           C.POINTER(C.c_size_t)]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
                                             vp, C.c_size_t, vp]
+    lib.vc2hip_stream_write_fragments_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams),
+                                                      C.POINTER(StreamParams), C.c_int, vp, C.c_size_t, vp, vp, C.c_size_t, vp]
     lib.vc2hip_stream_read_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
                                            vp, C.c_size_t, vp, vp, vp]
     lib.vc2hip_profile_enable.argtypes = [vp, C.c_int]
@@ -434,6 +436,13 @@ class Vc2Hip:
     def stream_write_dev(self, d_payload, stride, d_lens, n, cp, sp, d_stream, cap, d_stream_len):
         self._chk(self.lib.vc2hip_stream_write_dev(self.h, d_payload, stride, d_lens, n, C.byref(cp), C.byref(sp), d_stream,
                                                    cap, d_stream_len))
+
+    def stream_write_fragments_dev(self, d_payload, stride, d_lens, n, cp, sp, fragment_length, d_stream, cap, d_stream_len,
+                                   d_unit_offsets=None, unit_cap=0, d_unit_count=None):
+        """fragmented pictures (EncodeStream -F); the unit table (offsets, capacity, count) is optional"""
+        self._chk(self.lib.vc2hip_stream_write_fragments_dev(self.h, d_payload, stride, d_lens, n, C.byref(cp), C.byref(sp),
+                                                             fragment_length, d_stream, cap, d_stream_len, d_unit_offsets,
+                                                             unit_cap, d_unit_count))
 
     def stream_read_dev(self, d_stream, length, n, cp, sp, d_payload, stride, d_lens, d_picture_numbers=None, d_consumed=None):
         self._chk(self.lib.vc2hip_stream_read_dev(self.h, d_stream, length, n, C.byref(cp), C.byref(sp), d_payload, stride,

@@ -227,7 +227,8 @@ int vc2hip_decode_picture_begin(vc2hip_ctx *ctx, const uint8_t *payload, size_t 
 int vc2hip_decode_picture_end(vc2hip_ctx *ctx, int ticket);
 
 /* device-resident batches: n independent pictures per call, asynchronous on the ctx stream.
- *   d_raw       n * vc2hip_raw_picture_bytes() bytes of raw planar pictures (device memory)
+ *   d_raw       n * vc2hip_raw_picture_bytes() bytes of raw planar pictures (device memory), in the file format -- or as
+ *               vc2hip_set_sample_layout says, for every raw-sample buffer of the calls below
  *   d_payload   n slots of payload_stride bytes each (device memory)
  *   d_lens      n uint64 payload lengths (device memory; written by encode, read by decode)
  * d_raw, d_payload and payload_stride must be multiples of 16 bytes (VC2HIP_EINVAL otherwise); when a
@@ -268,6 +269,59 @@ int vc2hip_decode_picture_end(vc2hip_ctx *ctx, int ticket);
  * forked from and joined to the context's stream (k = 1: off, the default).  The launches of the sub-batches
  * overlap on the GPU; results are identical.  Extension, no counterpart in the reference. */
 int vc2hip_set_streams(vc2hip_ctx *ctx, int k);
+/* The caller's sample layout: where and how the raw words of the DEVICE BATCH CALLS lie.  The default is the reference's file
+ * format (Arrays.cpp:333-426): big-endian words, the sample in the top bit_depth bits, rows packed tight, Y, U and V back to
+ * back, pictures back to back.  A layout describes what lives on a GPU instead: a torch int16 / uint16 tensor (little-endian,
+ * sample in the low bits), a pitched allocation, a crop of a larger picture, planes with gaps between them.  The layout
+ * changes where samples lie, not what they are: payload bytes, lengths, indices, d_sse and decoded sample values are those
+ * of the same pictures in the file format, and the same kernels run (vc2hip_dwt_launches shows the same record).
+ *   little_endian, lsb_justified   0 / 1.  One-byte words: the byte order has no effect
+ *   pitch[c]          bytes from one row of component c to the next; 0 = tight (the component's width * word_bytes)
+ *   plane_offset[c]   bytes from a picture's base to its Y, U, V plane; all three 0 = back to back (U behind Y's last pitch-
+ *                     spaced row, V behind U's)
+ *   picture_stride    bytes from one picture's base to the next; 0 = packed: vc2hip_layout_picture_bytes
+ * Read: a sample is the bit_depth bits of its word at the layout's position (chroma: chroma_bit_depth where the encoder
+ * honours it); every other bit of the word is ignored -- for MSB-justified words the low bits (the rule of the file format),
+ * for LSB-justified words the high bits.  Written: every bit of a word outside the sample is zero, and no byte outside the
+ * rows of the planes is ever written: not the pitch gaps, not the bytes between planes, not those between pictures.
+ * Overlap of planes or pictures is not validated (row-interleaved planes are a legitimate layout); results are unspecified
+ * when written bytes overlap.
+ * The layout is context state, as vc2hip_set_streams is, and from the call on describes EVERY raw-sample buffer of every
+ * device batch call: d_raw, d_raw_out, d_recon (one layout for d_raw and d_recon; the overlap refusal uses the layout's
+ * extents), d_frames / d_frames_out (the layout is the FRAME's; the field addressing goes on top: field pitch = 2 x frame
+ * pitch, field step = +- one frame pitch), and the output of vc2hip_decode_reduced_batch_dev (the layout describes the
+ * REDUCED pictures' buffer: an explicit pitch must hold a reduced row).  n pictures span (n - 1) * picture stride +
+ * vc2hip_layout_picture_bytes bytes.  The base pointers keep their 16-byte alignment rule.
+ * The setter is pure host state: it launches nothing and waits for nothing, may be called between any two calls, a
+ * captured call keeps the layout it was captured with, and lanes (vc2hip_set_streams(k > 1)) use the context's layout.
+ * NULL (or an all-zero struct): the file format again.
+ * These keep the file format whatever the context's layout: the host-buffer picture calls (vc2hip_encode_picture_* /
+ * vc2hip_decode_picture_*), the pipelined calls (_begin / _end), the fine-grained int32 calls, the stream calls (they move
+ * payload bytes only) and the CLI tools.
+ * VC2HIP_EINVAL -- from the setter for a malformed struct, from the batch call where the check needs fmt; nothing is
+ * launched, no output byte is touched and the context keeps the layout it had: a flag other than 0 / 1; a non-zero pitch,
+ * plane offset or picture stride that is not a multiple of 16 bytes (the 16-byte raw loads and stores need that of every
+ * row, as for the field step); a pitch below the component's row bytes; a picture stride below
+ * vc2hip_layout_picture_bytes; a plane beyond the kernels' 32-bit row offsets: a pitch of 2^23 bytes or more, or rows *
+ * pitch of 2^31 bytes or more (the kernels form a row's offset as a 24-bit by 24-bit product of the row and the pitch in
+ * 16-bit words, plus the column, in 32 bits).
+ * Not covered: interleaved chroma (P210 / NV16-style UV pairs) and packed formats (v210).
+ * Extension, no counterpart in the reference. */
+typedef struct {
+  int little_endian;        /* 0: big-endian words (the file format); 1: little-endian */
+  int lsb_justified;        /* 0: the sample in the top bit_depth bits of the word (file format);
+                               1: in the low bits. Read: the bits above the depth are ignored.
+                               Written: they are zero */
+  size_t pitch[3];          /* bytes from one row to the next of Y, U, V; 0 = tight (width * word_bytes) */
+  size_t plane_offset[3];   /* bytes from a picture's base to its Y, U, V plane;
+                               all three 0 = back to back, as the file format */
+  size_t picture_stride;    /* bytes from one picture's base to the next; 0 = packed
+                               (the end of the furthest plane) */
+} vc2hip_sample_layout;
+int vc2hip_set_sample_layout(vc2hip_ctx *ctx, const vc2hip_sample_layout *layout); /* NULL: the file format again */
+/* Host arithmetic: bytes from a picture's base to the end of its furthest plane row.  NULL or an all-zero layout:
+ * vc2hip_raw_picture_bytes(fmt); 0 for a layout the calls would refuse for pictures of fmt. */
+size_t vc2hip_layout_picture_bytes(const vc2hip_picture_format *fmt, const vc2hip_sample_layout *layout);
 int vc2hip_encode_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
                             const vc2hip_picture_format *fmt, const vc2hip_coding_params *cp,
                             void *d_payload, size_t payload_stride, uint64_t *d_lens);

@@ -213,6 +213,10 @@ struct vc2hip_ctx {
   };
   Flight flight[VC2HIP_MAX_INFLIGHT];
   int flight_next = 0;               // slot of the next _begin
+  // vc2hip_set_sample_layout: where and how the raw words of the device batch calls lie (pure host state; has_layout false:
+  // the file format).  layout_bypass: a host-buffer picture call is running its batch call on the context -- file format.
+  vc2hip_sample_layout layout = {};
+  bool has_layout = false, layout_bypass = false;
 };
 
 static const char *code_text(int code) {
@@ -558,6 +562,7 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
   for (int i = 0; i < k; ++i) {
     vc2hip_ctx *l = c->lanes[i];
     c->in_split = (i == 0);
+    l->layout = c->layout; l->has_layout = c->has_layout; // (host state: a lane's pictures lie as the context's)
     const int r = fn(l, first[i], count[i]);
     c->in_split = false;
     if (r && !rc) rc = i ? set_err(c, r, l->err.c_str()) : r;
@@ -711,6 +716,92 @@ extern "C" size_t vc2hip_raw_picture_bytes(const vc2hip_picture_format *f) {
   chroma_dims(f->height, f->width, f->chroma_format, &ch, &cw);
   return ((size_t)f->height * f->width + 2 * (size_t)ch * cw) * f->word_bytes;
 }
+
+// ------------------------------------------------------------------------------------------
+// the caller's sample layout (vc2hip_set_sample_layout)
+// ------------------------------------------------------------------------------------------
+// A layout resolved against the pictures of one buffer: every 0 of the struct replaced by what it stands for.
+struct RawLayout {
+  int le, lsb;
+  size_t pitch[3], at[3]; // bytes from row to row; from a picture's base to the plane
+  size_t extent;          // from a picture's base to the end of its furthest plane row
+  size_t stride;          // from one picture's base to the next
+};
+// what the struct alone shows (the setter's check); null: the file format
+static const char *layout_struct_error(const vc2hip_sample_layout *l) {
+  if (!l) return nullptr;
+  if ((l->little_endian != 0 && l->little_endian != 1) || (l->lsb_justified != 0 && l->lsb_justified != 1))
+    return "sample layout: little_endian and lsb_justified must be 0 or 1";
+  size_t any = l->picture_stride;
+  for (int k = 0; k < 3; ++k) any |= l->pitch[k] | l->plane_offset[k];
+  if (any & 15) return "sample layout: pitches, plane offsets and the picture stride must be multiples of 16 bytes";
+  return nullptr;
+}
+// The 32-bit row offsets of the edge kernels (mul24z(y, pitch / 2) * 2, __umul24(y, pitch / 2) + column: 24-bit factors, a
+// 32-bit sum of 16-bit words) carry a plane whose rows lie below 2^23 bytes apart and whose extent stays below 2^31 bytes.
+#define VC2_LAYOUT_MAX_PITCH ((size_t)1 << 23)
+#define VC2_LAYOUT_MAX_PLANE ((size_t)1 << 31)
+// f: the format of the buffer's pictures (frames for the field calls, the reduced pictures for the reduced call).
+// l null: the file format, never refused.  Returns null, or why the calls refuse the layout for these pictures.
+static const char *resolve_layout(const vc2hip_picture_format *f, const vc2hip_sample_layout *l, RawLayout &r) {
+  int ch, cw;
+  chroma_dims(f->height, f->width, f->chroma_format, &ch, &cw);
+  const size_t row[3] = {(size_t)f->width * f->word_bytes, (size_t)cw * f->word_bytes, (size_t)cw * f->word_bytes};
+  const size_t rows[3] = {(size_t)f->height, (size_t)ch, (size_t)ch};
+  if (const char *e = layout_struct_error(l)) return e;
+  r.le = l ? l->little_endian : 0;
+  r.lsb = l ? l->lsb_justified : 0;
+  const bool placed = l && (l->plane_offset[0] | l->plane_offset[1] | l->plane_offset[2]);
+  const bool custom = l && (placed || l->little_endian || l->lsb_justified || l->picture_stride || l->pitch[0] || l->pitch[1] || l->pitch[2]);
+  r.extent = 0;
+  for (int k = 0; k < 3; ++k) {
+    r.pitch[k] = l && l->pitch[k] ? l->pitch[k] : row[k];
+    if (r.pitch[k] < row[k]) return "sample layout: a pitch below the component's row bytes";
+    if (custom && (r.pitch[k] >= VC2_LAYOUT_MAX_PITCH || rows[k] * r.pitch[k] >= VC2_LAYOUT_MAX_PLANE))
+      return "sample layout: a plane beyond the kernels' 32-bit row offsets (pitch below 2^23 bytes, rows * pitch below 2^31)";
+    r.at[k] = placed ? l->plane_offset[k] : k ? r.at[k - 1] + rows[k - 1] * r.pitch[k - 1] : 0;
+    const size_t end = rows[k] ? r.at[k] + (rows[k] - 1) * r.pitch[k] + row[k] : r.at[k];
+    if (end > r.extent) r.extent = end;
+  }
+  r.stride = l && l->picture_stride ? l->picture_stride : r.extent;
+  if (r.stride < r.extent) return "sample layout: a picture stride below vc2hip_layout_picture_bytes";
+  return nullptr;
+}
+static bool format_ok(const vc2hip_picture_format *f) {
+  return f && f->width >= 1 && f->height >= 1 && f->word_bytes >= 1 && f->word_bytes <= 4 && f->chroma_format >= 0 && f->chroma_format <= 2;
+}
+// the layout of the context's device batch calls: null = the file format
+static const vc2hip_sample_layout *active_layout(const vc2hip_ctx *c) { return c->has_layout && !c->layout_bypass ? &c->layout : nullptr; }
+// ... resolved for a buffer of pictures of format f; VC2HIP_EINVAL (nothing launched) where the check needs the format
+static int batch_layout(vc2hip_ctx *c, const vc2hip_picture_format *f, RawLayout &r) {
+  if (!format_ok(f)) return set_err(c, VC2HIP_EINVAL);
+  if (const char *e = resolve_layout(f, active_layout(c), r)) return set_err(c, VC2HIP_EINVAL, e);
+  return VC2HIP_OK;
+}
+
+extern "C" int vc2hip_set_sample_layout(vc2hip_ctx *c, const vc2hip_sample_layout *l) {
+  if (!c) return VC2HIP_EINVAL;
+  if (const char *e = layout_struct_error(l)) return set_err(c, VC2HIP_EINVAL, e);
+  bool any = false;
+  if (l) {
+    any = l->little_endian || l->lsb_justified || l->picture_stride;
+    for (int k = 0; k < 3; ++k) any = any || l->pitch[k] || l->plane_offset[k];
+  }
+  c->has_layout = any; // (an all-zero layout is the file format)
+  if (any) c->layout = *l;
+  return VC2HIP_OK;
+}
+extern "C" size_t vc2hip_layout_picture_bytes(const vc2hip_picture_format *f, const vc2hip_sample_layout *l) {
+  RawLayout r;
+  if (!format_ok(f) || resolve_layout(f, l, r)) return 0;
+  return r.extent;
+}
+struct LayoutBypass { // a host-buffer picture call: its pictures are in the file format whatever the context's layout
+  vc2hip_ctx *c; bool was;
+  explicit LayoutBypass(vc2hip_ctx *ctx) : c(ctx), was(ctx->layout_bypass) { c->layout_bypass = true; }
+  ~LayoutBypass() { c->layout_bypass = was; }
+};
+
 static size_t max_slice_bytes(int prefix, int scalar) { return (size_t)prefix + 4 + 3 * 255 * (size_t)scalar; }
 extern "C" size_t vc2hip_max_payload_bytes(const vc2hip_picture_format *f, const vc2hip_coding_params *cp) {
   (void)f;
@@ -818,11 +909,17 @@ static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const vo
       for (int k = 0; k < 3; ++k) { p.raw_pitch[k] = src_l[k].pitch; p.field_step[k] = src_l[k].field_step; }
       p.field_shift = src_l[0].field_shift;
       p.word_bytes = f->word_bytes;
-      p.sample_shift = 8 * f->word_bytes - f->bit_depth;
+      const int lsb = src_l[0].lsb; // the caller's sample layout (raw_planes): LSB-justified words need no shift
+      p.sample_shift = lsb ? 0 : 8 * f->word_bytes - f->bit_depth;
       p.sample_offset = 1 << (f->bit_depth - 1);
       const int cd = f->chroma_bit_depth ? f->chroma_bit_depth : f->bit_depth;
-      p.sample_shift_c = 8 * f->word_bytes - cd;
+      p.sample_shift_c = lsb ? 0 : 8 * f->word_bytes - cd;
       p.sample_offset_c = 1 << (cd - 1);
+      p.sample_bits = f->bit_depth; p.sample_bits_c = cd;
+      p.sample_mask = f->bit_depth < 32 ? (1u << f->bit_depth) - 1 : ~0u;
+      p.sample_mask_c = cd < 32 ? (1u << cd) - 1 : ~0u;
+      p.sample_le = src_l[0].le;
+      p.perm_rd = src_l[0].le ? VC2_PERM_RD_LE : VC2_PERM_RD_BE;
     }
   };
   for (int level = 0; level < g.depth; ++level) {
@@ -908,8 +1005,10 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
       for (int k = 0; k < 3; ++k) { p.raw_pitch[k] = dst_l[k].pitch; p.field_step[k] = dst_l[k].field_step; }
       p.field_shift = dst_l[0].field_shift;
       p.word_bytes = f->word_bytes;
-      p.sample_shift = 8 * f->word_bytes - f->bit_depth;
+      p.sample_shift = dst_l[0].lsb ? 0 : 8 * f->word_bytes - f->bit_depth; // (the clip keeps a sample inside its bits: every other bit is zero)
       p.sample_offset = 1 << (f->bit_depth - 1);
+      p.sample_le = dst_l[0].le;
+      p.perm_wr = dst_l[0].le ? VC2_PERM_WR_LE : VC2_PERM_WR_BE;
       p.clip_lo = -(1 << (f->bit_depth - 1));
       p.clip_hi = (1 << (f->bit_depth - 1)) - 1;
       p.norm_shift = norm_shift;
@@ -1623,19 +1722,21 @@ extern "C" int vc2hip_ld_pack(vc2hip_ctx *c, const int32_t *y, const int32_t *u,
 // The raw words of a batch of pictures of format f (vc2_raw_pic_offset).  fields == 1: progressive pictures, packed.
 // fields == 2: f is a FIELD's format, the pictures are the fields of packed interleaved frames (2 * f->height rows, and twice
 // the chroma rows), in stream order: the first field of a frame is its even rows when top_first, else its odd rows.
-static void raw_planes(const vc2hip_picture_format *f, const void *base, int fields, int top_first, const void *pl[3], RawPlane rl[3]) {
-  int ch, cw;
-  chroma_dims(f->height, f->width, f->chroma_format, &ch, &cw);
-  const size_t ln = (size_t)f->height * f->width * f->word_bytes, cn = (size_t)ch * cw * f->word_bytes;
-  const int row[3] = {f->width * f->word_bytes, cw * f->word_bytes, cw * f->word_bytes};
-  const size_t at[3] = {0, fields * ln, fields * (ln + cn)};
+// lay: the caller's sample layout (null: the file format).  It describes the FRAME's buffer; the field addressing goes on top.
+static void raw_planes(const vc2hip_picture_format *f, const vc2hip_sample_layout *lay, const void *base, int fields, int top_first,
+                       const void *pl[3], RawPlane rl[3]) {
+  vc2hip_picture_format ff = *f; // the pictures of the buffer
+  ff.height = f->height * fields;
+  RawLayout r;
+  (void)resolve_layout(&ff, lay, r); // (refused by the entry points: batch_layout)
   for (int k = 0; k < 3; ++k) {
     const bool second_first = fields == 2 && !top_first; // (the first field starts on the frame's row 1)
-    pl[k] = (const uint8_t *)base + at[k] + (second_first ? row[k] : 0);
-    rl[k].stride = (long long)fields * (ln + 2 * cn);
-    rl[k].pitch = fields * row[k];
-    rl[k].field_step = fields == 2 ? (top_first ? row[k] : -row[k]) : 0;
+    pl[k] = (const uint8_t *)base + r.at[k] + (second_first ? r.pitch[k] : 0);
+    rl[k].stride = (long long)r.stride;
+    rl[k].pitch = fields * (int)r.pitch[k];
+    rl[k].field_step = fields == 2 ? (top_first ? (int)r.pitch[k] : -(int)r.pitch[k]) : 0;
     rl[k].field_shift = fields == 2;
+    rl[k].le = r.le; rl[k].lsb = r.lsb;
   }
 }
 
@@ -1738,8 +1839,10 @@ extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, 
   if (!c || !d_raw || n < 1 || !f || !cp || !d_payload || !d_lens) return set_err(c, VC2HIP_EINVAL);
   if (((size_t)d_raw | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
     return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  RawLayout lay;
+  if (int rc = batch_layout(c, f, lay)) return rc;
   if (c->lanes.size() > 1 && n > 1 && !c->in_split) {
-    const size_t rb = vc2hip_raw_picture_bytes(f);
+    const size_t rb = lay.stride; // (the file format: vc2hip_raw_picture_bytes)
     const uint8_t *raw8 = (const uint8_t *)d_raw, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
     return split_batch(c, n,
       [&](int first, int count, vc2hip_ctx::LaneUse &u) {
@@ -1771,12 +1874,14 @@ extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, i
     return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
   Geom ge;
   if (picture_geom(ge, f, cp, false)) return set_err(c, VC2HIP_EINVAL);
-  const size_t rb = vc2hip_raw_picture_bytes(f);
+  RawLayout lay; // one layout for d_raw and d_recon
+  if (int rc = batch_layout(c, f, lay)) return rc;
+  const size_t rb = lay.stride, span = (size_t)(n - 1) * lay.stride + lay.extent; // (the file format: n * vc2hip_raw_picture_bytes)
   const int ns = ge.ys * ge.xs;
   const uint8_t *raw8 = (const uint8_t *)d_raw;
   uint8_t *rec8 = (uint8_t *)d_recon;
   if (d_recon) {
-    if (rec8 < raw8 + (size_t)n * rb && raw8 < rec8 + (size_t)n * rb)
+    if (rec8 < raw8 + span && raw8 < rec8 + span)
       return set_err(c, VC2HIP_EINVAL, "d_recon overlaps d_raw (the squared error reads the input after the reconstruction is written)");
     if (f->chroma_bit_depth && f->chroma_bit_depth != f->bit_depth)
       return set_err(c, VC2HIP_EINVAL, "the decoder has one bit depth: chroma_bit_depth must be 0 or bit_depth with d_recon");
@@ -1816,10 +1921,16 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
   if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD) return set_err(c, VC2HIP_EINVAL);
   if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
   if (cp->mode != VC2HIP_LD && (cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
-  ENTER(c);
   Geom g;
   int rc = picture_geom(g, f, cp, false);
   if (rc) return set_err(c, rc);
+  { // the caller's sample layout against the buffer's pictures (frames, for fields): refused before anything is enqueued
+    vc2hip_picture_format fb = *f;
+    fb.height = f->height * fields;
+    RawLayout lay;
+    if ((rc = batch_layout(c, &fb, lay))) return rc;
+  }
+  ENTER(c);
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
   if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
@@ -1835,7 +1946,7 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
   LLPlanes ll;
   ll_layout(g, n, d_ll, s16 ? 2 : 4, d_llw, ll);
   const void *src[3]; RawPlane ss[3];
-  raw_planes(f, d_raw, fields, top_first, src, ss);
+  raw_planes(f, active_layout(c), d_raw, fields, top_first, src, ss);
   if (needs_plane_path(c, g, cp->kernel)) { // (a slice beyond any LDS tile: HQ and LD alike -- the store is int32 then)
     if ((rc = plane_forward(c, g, cp->kernel, n, src, ss, f, d_store))) return rc;
   } else if ((rc = run_forward(c, g, cp->kernel, n, src, ss, true, f, d_store, ll, s16, d_storew))) return rc;
@@ -1907,7 +2018,7 @@ static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *c
   int rc;
   if (ro.qidx) HIPCHK(c, hipMemcpyAsync(ro.qidx, d_q, (size_t)n * ns * 4, hipMemcpyDeviceToDevice, c->stream));
   const void *dstc[3]; RawPlane ds[3];
-  raw_planes(f, ro.recon, 1, 1, dstc, ds);
+  raw_planes(f, active_layout(c), ro.recon, 1, 1, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
   if (ld) {
@@ -1963,14 +2074,20 @@ static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *c
     SseParams p;
     memset(&p, 0, sizeof p);
     p.a = (const uint8_t *)d_raw; p.b = (const uint8_t *)ro.recon;
-    p.pic_bytes = (long long)vc2hip_raw_picture_bytes(f);
-    long long at = 0;
+    RawLayout lay;
+    (void)resolve_layout(f, active_layout(c), lay); // (refused at the entry point)
+    p.pic_bytes = (long long)lay.stride;
     for (int k = 0; k < 3; ++k) {
-      p.comp_at[k] = at;
-      p.comp_bytes[k] = (long long)g.c[k].h * g.c[k].w * f->word_bytes;
-      at += p.comp_bytes[k];
+      const long long row = (long long)g.c[k].w * f->word_bytes;
+      const bool tight = (long long)lay.pitch[k] == row; // one run of bytes: the kernel's "one row"
+      p.comp_at[k] = (long long)lay.at[k];
+      p.rows[k] = tight ? 1 : g.c[k].h;
+      p.row_bytes[k] = tight ? row * g.c[k].h : row;
+      p.pitch[k] = (long long)lay.pitch[k];
     }
-    p.word_bytes = f->word_bytes; p.shift = 8 * f->word_bytes - f->bit_depth;
+    p.word_bytes = f->word_bytes; p.shift = lay.lsb ? 0 : 8 * f->word_bytes - f->bit_depth;
+    p.mask = f->bit_depth < 32 ? (1u << f->bit_depth) - 1 : ~0u;
+    p.le = lay.le;
     p.sse = (unsigned long long *)ro.sse;
     vc2_launch_squared_error(c->L, p, n, c->stream);
   }
@@ -1984,10 +2101,16 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   if (((size_t)d_raw_out | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
     return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
   if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
-  ENTER(c);
   Geom g;
   int rc = picture_geom(g, f, cp, true);
   if (rc) return set_err(c, rc);
+  { // the caller's sample layout against the pictures of d_raw_out (frames, for fields; the reduced pictures): as the encoder
+    vc2hip_picture_format fb = *f;
+    fb.height = (f->height * fields) >> drop; fb.width = f->width >> drop;
+    RawLayout lay;
+    if ((rc = batch_layout(c, &fb, lay))) return rc;
+  }
+  ENTER(c);
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
   if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
@@ -2015,7 +2138,7 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   }
   const bool s16 = !ld && use_store16(c, g, cp->kernel);
   const void *dstc[3]; RawPlane ds[3];
-  raw_planes(f, d_raw_out, fields, top_first, dstc, ds);
+  raw_planes(f, active_layout(c), d_raw_out, fields, top_first, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
   DecoderLayout lay;
@@ -2355,7 +2478,9 @@ extern "C" int vc2hip_dwt_launches(const vc2hip_ctx *c, vc2hip_dwt_launch *out, 
 extern "C" int vc2hip_decode_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
                                        int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out) {
   if (c && c->lanes.size() > 1 && n > 1 && !c->in_split && d_payload && f && cp && d_raw_out) {
-    const size_t rb = vc2hip_raw_picture_bytes(f);
+    RawLayout lay;
+    if (int rc = batch_layout(c, f, lay)) return rc;
+    const size_t rb = lay.stride;
     const uint8_t *out8 = (const uint8_t *)d_raw_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
     return split_batch(c, n,
       [&](int first, int count, vc2hip_ctx::LaneUse &u) {
@@ -2396,7 +2521,9 @@ extern "C" int vc2hip_decode_reduced_batch_dev(vc2hip_ctx *c, const void *d_payl
   if (c->lanes.size() > 1 && n > 1 && !c->in_split) {
     vc2hip_picture_format fr = *f;
     fr.width = f->width >> drop_levels; fr.height = f->height >> drop_levels;
-    const size_t rb = vc2hip_raw_picture_bytes(&fr);
+    RawLayout lay; // (of the reduced pictures' buffer)
+    if (int rc2 = batch_layout(c, &fr, lay)) return rc2;
+    const size_t rb = lay.stride;
     const uint8_t *out8 = (const uint8_t *)d_raw_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
     return split_batch(c, n,
       [&](int first, int count, vc2hip_ctx::LaneUse &u) {
@@ -2436,7 +2563,9 @@ extern "C" int vc2hip_encode_fields_batch_dev(vc2hip_ctx *c, const void *d_frame
   int rc = field_format(c, frame_fmt, &ff);
   if (rc) return rc;
   if (c->lanes.size() > 1 && n_frames > 1 && !c->in_split) { // whole frames per lane: frames [first, first + count), slots twice that
-    const size_t fb = vc2hip_raw_picture_bytes(frame_fmt);
+    RawLayout lay; // (the FRAME's)
+    if ((rc = batch_layout(c, frame_fmt, lay))) return rc;
+    const size_t fb = lay.stride;
     const uint8_t *raw8 = (const uint8_t *)d_frames, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
     return split_batch(c, n_frames,
       [&](int first, int count, vc2hip_ctx::LaneUse &u) {
@@ -2462,7 +2591,9 @@ extern "C" int vc2hip_decode_fields_batch_dev(vc2hip_ctx *c, const void *d_paylo
   int rc = field_format(c, frame_fmt, &ff);
   if (rc) return rc;
   if (c->lanes.size() > 1 && n_frames > 1 && !c->in_split) {
-    const size_t fb = vc2hip_raw_picture_bytes(frame_fmt);
+    RawLayout lay;
+    if ((rc = batch_layout(c, frame_fmt, lay))) return rc;
+    const size_t fb = lay.stride;
     const uint8_t *out8 = (const uint8_t *)d_frames_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
     return split_batch(c, n_frames,
       [&](int first, int count, vc2hip_ctx::LaneUse &u) {
@@ -2491,6 +2622,7 @@ extern "C" int vc2hip_encode_picture_hq(vc2hip_ctx *c, const void *raw, const vc
   NEED(c, B_PAYLOAD, pcap + 64, d_pay);
   NEED(c, B_LENS, 64, d_len);
   HIPCHK(c, hipMemcpyAsync(d_raw, raw, rb, hipMemcpyHostToDevice, c->stream));
+  const LayoutBypass file_format(c); // (the host-buffer calls keep the file format)
   int rc = vc2hip_encode_batch_dev(c, d_raw, 1, f, cp, d_pay, pcap, (uint64_t *)d_len);
   if (rc) return rc;
   unsigned long long l = 0;
@@ -2524,6 +2656,7 @@ static int decode_picture_host(vc2hip_ctx *c, const uint8_t *payload, size_t len
   unsigned long long l64 = len;
   HIPCHK(c, hipMemcpyAsync(d_pay, payload, len, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_len, &l64, 8, hipMemcpyHostToDevice, c->stream));
+  const LayoutBypass file_format(c); // (the host-buffer calls keep the file format)
   int rc = decode_batch_common(c, d_pay, stride, (const uint64_t *)d_len, 1, f, cp, d_raw, ld);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(raw_out, d_raw, rb, hipMemcpyDeviceToHost, c->stream));

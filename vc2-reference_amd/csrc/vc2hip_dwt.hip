@@ -137,15 +137,9 @@ __global__ __launch_bounds__(256) void k_fwd_level(const LevelParams p) {
         const int sy = min(gy, p.pic_h[comp] - 1), sx = min(gx, p.pic_w[comp] - 1);
         const uint8_t *src = (const uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +
                              (size_t)sy * p.raw_pitch[comp] + (size_t)sx * p.word_bytes;
-        unsigned u;
-        if (p.word_bytes == 2) {
-          const unsigned short h = *(const unsigned short *)src;
-          u = ((h & 0xFF) << 8) | (h >> 8);
-        } else {
-          u = 0;
-          for (int b = 0; b < p.word_bytes; ++b) u = (u << 8) | src[b];
-        }
-        v = (int)(u >> (comp ? p.sample_shift_c : p.sample_shift)) - (comp ? p.sample_offset_c : p.sample_offset);
+        const unsigned u = vc2_load_word(src, p.word_bytes, p.sample_le);
+        v = (int)((u >> (comp ? p.sample_shift_c : p.sample_shift)) & (comp ? p.sample_mask_c : p.sample_mask)) -
+            (comp ? p.sample_offset_c : p.sample_offset);
       } else {
         v = ((const int32_t *)p.plane[comp])[(size_t)pic * p.plane_stride[comp] + (size_t)gy * in_w + gx];
       }
@@ -262,11 +256,7 @@ __global__ __launch_bounds__(256) void k_inv_level(const LevelParams p) {
       const unsigned u = (unsigned)(v + p.sample_offset) << p.sample_shift;
       uint8_t *dst = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +
                      (size_t)gy * p.raw_pitch[comp] + (size_t)gx * p.word_bytes;
-      if (p.word_bytes == 2) {
-        *(unsigned short *)dst = (unsigned short)(((u & 0xFF) << 8) | ((u >> 8) & 0xFF));
-      } else {
-        for (int b = 0; b < p.word_bytes; ++b) dst[b] = (uint8_t)(u >> (8 * (p.word_bytes - 1 - b)));
-      }
+      vc2_store_word(dst, u, p.word_bytes, p.sample_le);
     } else {
       ((int32_t *)p.plane[comp])[(size_t)pic * p.plane_stride[comp] + (size_t)gy * out_w + gx] = v;
     }

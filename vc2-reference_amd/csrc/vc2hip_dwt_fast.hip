@@ -443,9 +443,9 @@ __global__ __launch_bounds__(NTK<K>) void k_fwd_fast(const LevelParams p) {
           const unsigned wv[4] = {va[it].x, va[it].y, va[it].z, va[it].w};
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const unsigned b = __builtin_bswap32(wv[k]);
-            s[2 * k] = (int)(b >> 16);
-            s[2 * k + 1] = (int)(b & 0xFFFFu);
+            const unsigned b = __builtin_amdgcn_perm(wv[k], wv[k], p.perm_rd); // both words to host order, the first in the low half
+            s[2 * k] = (int)(b & 0xFFFFu);
+            s[2 * k + 1] = (int)(b >> 16);
           }
         } else {
           const uint8_t *row = (const uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) +
@@ -454,14 +454,13 @@ __global__ __launch_bounds__(NTK<K>) void k_fwd_fast(const LevelParams p) {
           for (int k = 0; k < 8; ++k) {
             const int sx = min(max(gx0 + k, 0), pic_w - 1);
             const uint8_t *q = row + (size_t)sx * p.word_bytes;
-            unsigned u = 0;
-            for (int b = 0; b < p.word_bytes; ++b) u = (u << 8) | q[b];
-            s[k] = (int)u;
+            s[k] = (int)vc2_load_word(q, p.word_bytes, p.sample_le);
           }
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-          s[k] = (int)((unsigned)((int)((unsigned)s[k] >> (comp ? p.sample_shift_c : p.sample_shift)) - (comp ? p.sample_offset_c : p.sample_offset)) << ACC);
+          s[k] = (int)((unsigned)((int)(((unsigned)s[k] >> (comp ? p.sample_shift_c : p.sample_shift)) & (comp ? p.sample_mask_c : p.sample_mask)) -
+                                  (comp ? p.sample_offset_c : p.sample_offset)) << ACC);
       } else {
         if (kind[it] == 1) {
           if constexpr (S_::narrow) S_::unpack8(va[it], lvl_w + (size_t)gy * in_w + gx0, s);
@@ -1046,13 +1045,13 @@ __global__ __launch_bounds__(NTK<K>) void k_inv_fast(const LevelParams p) {
       if (vec_out && gx0 + 8 <= lim_w) {
         unsigned wv[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) wv[k] = __builtin_bswap32(((u[2 * k] & 0xFFFFu) << 16) | (u[2 * k + 1] & 0xFFFFu));
+        for (int k = 0; k < 4; ++k) wv[k] = __builtin_amdgcn_perm(u[2 * k + 1], u[2 * k], p.perm_wr); // (the clip keeps a sample inside its word)
         *(uint4 *)(row + (size_t)gx0 * 2) = make_uint4(wv[0], wv[1], wv[2], wv[3]);
       } else {
         for (int k = 0; k < 8; ++k) {
           if (gx0 + k >= lim_w) break;
           uint8_t *q = row + (size_t)(gx0 + k) * p.word_bytes;
-          for (int b2 = 0; b2 < p.word_bytes; ++b2) q[b2] = (uint8_t)(u[k] >> (8 * (p.word_bytes - 1 - b2)));
+          vc2_store_word(q, u[k], p.word_bytes, p.sample_le);
         }
       }
     } else {

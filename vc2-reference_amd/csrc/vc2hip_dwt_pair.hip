@@ -119,6 +119,8 @@ __global__ __launch_bounds__(64, (pair_wpe<K>())) void k_fwd_pair(const PairPara
 #endif
   const int pieceA = pp.piece_a[comp], pieceB = pp.piece_b[comp];
   const int sshift = FIRST ? (comp ? p.sample_shift_c : p.sample_shift) : 0;
+  const int sbits = FIRST ? (comp ? p.sample_bits_c : p.sample_bits) : 0;
+  const unsigned sel_rd = p.perm_rd; // the layout's byte order (wave-uniform, as the shift)
   const int bias = FIRST ? -((comp ? p.sample_offset_c : p.sample_offset) << ACC) : 0;
   const int in_h = p.in_h[comp], in_w = p.in_w[comp], npA = in_h >> 1, npB = npA >> 1;
   const int chunk = min(sp.c0 + lane, (in_w >> 3) - 1);
@@ -155,9 +157,9 @@ __global__ __launch_bounds__(64, (pair_wpe<K>())) void k_fwd_pair(const PairPara
       const unsigned w[4] = {pf[slot][h][0].x, pf[slot][h][0].y, pf[slot][h][0].z, pf[slot][h][0].w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const unsigned b = __builtin_amdgcn_perm(w[k], w[k], 0x02030001u); // both big-endian 16-bit words to host order
-        r[k] = (int)(((b & 0xFFFFu) >> sshift) << ACC) + bias;
-        r[4 + k] = (int)((b >> (16 + sshift)) << ACC) + bias;
+        const unsigned b = __builtin_amdgcn_perm(w[k], w[k], sel_rd); // both 16-bit words to host order, the first in the low half
+        r[k] = (int)(__builtin_amdgcn_ubfe(b, (unsigned)sshift, (unsigned)sbits) << ACC) + bias; // (the bits outside the sample are ignored)
+        r[4 + k] = (int)(__builtin_amdgcn_ubfe(b, (unsigned)(16 + sshift), (unsigned)sbits) << ACC) + bias;
       }
     } else {
       int s[8];
@@ -794,6 +796,7 @@ __global__ __launch_bounds__(64, (K == VC2HIP_DD137 || SPL2 ? 2 : VC2_PAIR_WPE_I
   // ---- output rows of level a (as k_inv_stream)
   const int lim_h = FINAL ? p.pic_h[comp] : out_h;
   const int clip_lo = p.clip_lo, clip_hi = p.clip_hi, sample_offset = p.sample_offset, sample_shift = p.sample_shift, norm_shift = p.norm_shift;
+  const unsigned sel_wr = p.perm_wr;
   uint8_t *rawo = nullptr; // (this picture's output plane; the lane's columns are part of the offset)
   ST *lvl = nullptr;
   int32_t *lvl_w = nullptr;
@@ -823,7 +826,7 @@ __global__ __launch_bounds__(64, (K == VC2HIP_DD137 || SPL2 ? 2 : VC2_PAIR_WPE_I
       for (int k = 0; k < 4; ++k) {
         const unsigned a = (unsigned)(min(max(s[2 * k], clip_lo), clip_hi) + sample_offset) << sample_shift;
         const unsigned b = (unsigned)(min(max(s[2 * k + 1], clip_lo), clip_hi) + sample_offset) << sample_shift;
-        o.w[k] = __builtin_amdgcn_perm(b, a, 0x04050001u); // the low halves of a, b as big-endian 16-bit words (pack and swap in one v_perm)
+        o.w[k] = __builtin_amdgcn_perm(b, a, sel_wr); // the low halves of a, b as the layout's 16-bit words (pack and byte order in one v_perm)
       }
     } else if constexpr (S_::narrow) {
       const int mx = max(max(max(s[0], s[1]), max(s[2], s[3])), max(max(s[4], s[5]), max(s[6], s[7])));

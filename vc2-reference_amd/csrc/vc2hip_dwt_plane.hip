@@ -17,18 +17,17 @@ namespace {
 // raw planar words -> padded int32 plane (Arrays.cpp:333-379 + waveletPad, WaveletTransform.cpp:79-94)
 // (raw_stride / raw_pitch / field_step / field_shift: vc2_raw_pic_offset, as LevelParams)
 __global__ void k_plane_ingest(const uint8_t *raw, long long raw_stride, int raw_pitch, int field_step, int field_shift, int pic_h, int pic_w,
-                               int word_bytes, int shift, int offset, int32_t *plane, long long plane_stride, int ph, int pw) {
+                               int word_bytes, int le, int shift, unsigned mask, int offset, int32_t *plane, long long plane_stride, int ph, int pw) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, pic = blockIdx.z;
   if (x >= pw) return;
   const uint8_t *q = raw + vc2_raw_pic_offset(raw_stride, field_step, field_shift, pic) + (size_t)min(y, pic_h - 1) * raw_pitch +
                      (size_t)min(x, pic_w - 1) * word_bytes;
-  unsigned u = 0;
-  for (int b = 0; b < word_bytes; ++b) u = (u << 8) | q[b];
-  plane[(size_t)pic * plane_stride + (size_t)y * pw + x] = (int)(u >> shift) - offset;
+  const unsigned u = vc2_load_word(q, word_bytes, le);
+  plane[(size_t)pic * plane_stride + (size_t)y * pw + x] = (int)((u >> shift) & mask) - offset;
 }
 // int32 plane -> raw planar words, clipped (Picture.cpp:284-292, Arrays.cpp:381-426); the padding is cropped
 __global__ void k_plane_emit(const int32_t *plane, long long plane_stride, int pw, uint8_t *raw, long long raw_stride, int raw_pitch,
-                             int field_step, int field_shift, int pic_h, int pic_w, int word_bytes, int shift, int offset, int lo, int hi, int norm) {
+                             int field_step, int field_shift, int pic_h, int pic_w, int word_bytes, int le, int shift, int offset, int lo, int hi, int norm) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, pic = blockIdx.z;
   if (x >= pic_w) return;
   int v = plane[(size_t)pic * plane_stride + (size_t)y * pw + x];
@@ -36,7 +35,7 @@ __global__ void k_plane_emit(const int32_t *plane, long long plane_stride, int p
   v = min(max(v, lo), hi);
   const unsigned u = (unsigned)(v + offset) << shift;
   uint8_t *q = raw + vc2_raw_pic_offset(raw_stride, field_step, field_shift, pic) + (size_t)y * raw_pitch + (size_t)x * word_bytes;
-  for (int b = 0; b < word_bytes; ++b) q[b] = (uint8_t)(u >> (8 * (word_bytes - 1 - b)));
+  vc2_store_word(q, u, word_bytes, le);
 }
 // the accuracy shift of a level over its view: forward << acc before the level, inverse (x + 2^(acc-1)) >> acc after it
 template <bool INV> __global__ void k_plane_shift(int32_t *plane, long long plane_stride, int pw, int level, int vh, int vw, int acc) {
@@ -138,13 +137,14 @@ void vc2_launch_plane_ingest(Launcher &L, const void *raw, const RawPlane &rl, i
                              int32_t *plane, long long plane_stride, int ph, int pw, int n, hipStream_t s) {
   vc2_prof_begin(L, "plane_ingest", s);
   VC2_LAUNCH(L, k_plane_ingest, dim3((pw + 127) / 128, ph, n), dim3(128), 0, s, (const uint8_t *)raw, rl.stride, rl.pitch, rl.field_step,
-             rl.field_shift, pic_h, pic_w, word_bytes, 8 * word_bytes - bit_depth, 1 << (bit_depth - 1), plane, plane_stride, ph, pw);
+             rl.field_shift, pic_h, pic_w, word_bytes, rl.le, rl.lsb ? 0 : 8 * word_bytes - bit_depth, bit_depth < 32 ? (1u << bit_depth) - 1 : ~0u,
+             1 << (bit_depth - 1), plane, plane_stride, ph, pw);
   vc2_prof_end(L, s);
 }
 void vc2_launch_plane_emit(Launcher &L, const int32_t *plane, long long plane_stride, int pw, void *raw, const RawPlane &rl, int pic_h,
                            int pic_w, int word_bytes, int bit_depth, int n, hipStream_t s, int norm) {
   vc2_prof_begin(L, "plane_emit", s);
   VC2_LAUNCH(L, k_plane_emit, dim3((pic_w + 127) / 128, pic_h, n), dim3(128), 0, s, plane, plane_stride, pw, (uint8_t *)raw, rl.stride,
-             rl.pitch, rl.field_step, rl.field_shift, pic_h, pic_w, word_bytes, 8 * word_bytes - bit_depth, 1 << (bit_depth - 1), -(1 << (bit_depth - 1)), (1 << (bit_depth - 1)) - 1, norm);
+             rl.pitch, rl.field_step, rl.field_shift, pic_h, pic_w, word_bytes, rl.le, rl.lsb ? 0 : 8 * word_bytes - bit_depth, 1 << (bit_depth - 1), -(1 << (bit_depth - 1)), (1 << (bit_depth - 1)) - 1, norm);
   vc2_prof_end(L, s);
 }

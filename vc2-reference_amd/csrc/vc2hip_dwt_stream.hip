@@ -102,6 +102,12 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
   }
   const int pic_h = FIRST ? p.pic_h[comp] : in_h;
   const int rpw = FIRST ? p.raw_pitch[comp] >> 1 : in_w; // raw row pitch in 16-bit words (in_w, or two frame rows of a field)
+  // the raw words' format, wave-uniform and read once: chroma words may have their own depth; the byte order is the selector of
+  // a v_perm, the sample a bit field of its word (the caller's sample layout: vc2hip_set_sample_layout)
+  const int sshift = FIRST ? (comp ? p.sample_shift_c : p.sample_shift) : 0;
+  const int sbits = FIRST ? (comp ? p.sample_bits_c : p.sample_bits) : 0;
+  const unsigned sel = p.perm_rd;
+  const int bias = FIRST ? -((comp ? p.sample_offset_c : p.sample_offset) << ACC) : 0;
   constexpr int NQ = (FIRST || S_::narrow) ? 1 : 2; // 16-byte loads per row
   uint4 pf[PF][2][NQ];
   auto fetch = [&](int m, int slot) __attribute__((always_inline)) {
@@ -119,13 +125,11 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
   auto convert = [&](int m, int slot, int h, Row &r) __attribute__((always_inline)) {
     if constexpr (FIRST) {
       const unsigned w[4] = {pf[slot][h][0].x, pf[slot][h][0].y, pf[slot][h][0].z, pf[slot][h][0].w};
-      const int sshift = comp ? p.sample_shift_c : p.sample_shift; // (wave-uniform: chroma words may have their own depth)
-      const int bias = -((comp ? p.sample_offset_c : p.sample_offset) << ACC);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const unsigned b = __builtin_amdgcn_perm(w[k], w[k], 0x02030001u); // both big-endian 16-bit words to host order
-        r[k] = (int)(((b & 0xFFFFu) >> sshift) << ACC) + bias;
-        r[4 + k] = (int)((b >> (16 + sshift)) << ACC) + bias;
+        const unsigned b = __builtin_amdgcn_perm(w[k], w[k], sel); // both 16-bit words to host order, the first in the low half
+        r[k] = (int)(__builtin_amdgcn_ubfe(b, (unsigned)sshift, (unsigned)sbits) << ACC) + bias; // (the bits outside the sample are ignored)
+        r[4 + k] = (int)(__builtin_amdgcn_ubfe(b, (unsigned)(16 + sshift), (unsigned)sbits) << ACC) + bias;
       }
     } else {
       int s[8];
@@ -606,6 +610,7 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
   ST *lvl = nullptr;
   int32_t *lvl_w = nullptr;
   const int rpw = FINAL ? p.raw_pitch[comp] >> 1 : out_w; // raw row pitch in 16-bit words (as the forward kernel)
+  const unsigned sel_wr = p.perm_wr; // the layout's byte order (wave-uniform, read once)
   if constexpr (FINAL) rawo = (uint8_t *)p.plane[comp] + vc2_raw_pic_offset(p, comp, pic) + (size_t)chunk * 16;
   else {
     lvl = (ST *)p.plane[comp] + (size_t)pic * p.plane_stride[comp] + (size_t)chunk * 8;
@@ -633,7 +638,7 @@ __global__ __launch_bounds__(64 * VC2_STREAM_WG_WAVES, (stream_wpe<K, TAIL>())) 
       for (int k = 0; k < 4; ++k) {
         const unsigned a = (unsigned)(min(max(s[2 * k], p.clip_lo), p.clip_hi) + p.sample_offset) << p.sample_shift;
         const unsigned b = (unsigned)(min(max(s[2 * k + 1], p.clip_lo), p.clip_hi) + p.sample_offset) << p.sample_shift;
-        o.w[k] = __builtin_amdgcn_perm(b, a, 0x04050001u); // the low halves of a, b as big-endian 16-bit words (pack and swap in one v_perm)
+        o.w[k] = __builtin_amdgcn_perm(b, a, sel_wr); // the low halves of a, b as the layout's 16-bit words (pack and byte order in one v_perm)
       }
     } else if constexpr (S_::narrow) {
       const int mx = max(max(max(s[0], s[1]), max(s[2], s[3])), max(max(s[4], s[5]), max(s[6], s[7])));

@@ -120,6 +120,14 @@ struct LevelParams {
                               // slice's -- slice_coefs in the slice records, HeadSplit::n[c] in the record heads
   int word_bytes, sample_shift, sample_offset; // raw sample format (luma; the decoder's one format)
   int sample_shift_c, sample_offset_c;         // FIRST: the chroma words' (EncodeStream -c: its own depth)
+  // The caller's sample layout (vc2hip_set_sample_layout).  A sample is sample_bits bits of its word
+  // from bit sample_shift up (MSB-justified words: 8 * word_bytes - depth; LSB-justified: 0); FIRST ignores every other bit.
+  int sample_bits, sample_bits_c;              // FIRST: the depth of the luma / chroma words
+  unsigned sample_mask, sample_mask_c;         // FIRST: (1 << sample_bits) - 1 (all ones at 32 bits)
+  int sample_le;                               // the words are little-endian (the byte loops; one-byte words: no effect)
+  // 16-bit words, two per dword: the v_perm selectors of the byte order.  perm_rd: perm(w, w, perm_rd) has the first word of the
+  // dword w in its low half; perm_wr: perm(b, a, perm_wr) is the low halves of a (first) and b as the layout's words.
+  unsigned perm_rd, perm_wr;
   int clip_lo, clip_hi;
   int ll_from_store;          // inverse, coarsest level: LL comes from store band 0 (dequantised)
   int ll_to_store;            // forward, last level: LL goes to store band 0
@@ -163,7 +171,22 @@ __host__ __device__ __forceinline__ long long vc2_raw_pic_offset(const LevelPara
 struct RawPlane {
   long long stride;
   int pitch, field_step, field_shift;
+  int le, lsb; // the words' byte order and justification (vc2hip_sample_layout; 0, 0: the file format)
 };
+#define VC2_PERM_RD_BE 0x02030001u
+#define VC2_PERM_RD_LE 0x03020100u
+#define VC2_PERM_WR_BE 0x04050001u
+#define VC2_PERM_WR_LE 0x05040100u
+// one raw word of wb bytes in the layout's byte order (the element-wise paths of every FIRST / FINAL form)
+__device__ __forceinline__ unsigned vc2_load_word(const uint8_t *q, int wb, int le) {
+  unsigned u = 0;
+  if (le) for (int b = 0; b < wb; ++b) u |= (unsigned)q[b] << (8 * b);
+  else for (int b = 0; b < wb; ++b) u = (u << 8) | q[b];
+  return u;
+}
+__device__ __forceinline__ void vc2_store_word(uint8_t *q, unsigned u, int wb, int le) {
+  for (int b = 0; b < wb; ++b) q[b] = (uint8_t)(u >> (8 * (le ? b : wb - 1 - b)));
+}
 
 // Two consecutive levels in one launch (vc2hip_dwt_pair.hip): `a` is the finer level exactly as the one-level kernels see
 // it (its st_* fields describe the wavefronts: a lane holds 8 samples of level a's input plane), `b` the level below it
@@ -461,10 +484,14 @@ void vc2_launch_requantise(Launcher &L, const RequantParams &p, int n_pictures, 
 void vc2_launch_ld_check(Launcher &L, const LdEncParams &p, int n_pictures, hipStream_t s);
 // sums of squared sample differences of two raw buffers, per picture and component: sse[3 * pic + comp] += ...
 struct SseParams {
-  const uint8_t *a, *b;       // n pictures each, packed; both 16-byte aligned
-  long long pic_bytes;
-  long long comp_at[3], comp_bytes[3]; // a component's words inside a picture
-  int word_bytes, shift;      // sample = big-endian word >> shift
+  const uint8_t *a, *b;       // n pictures each, in one layout; both 16-byte aligned
+  long long pic_bytes;        // from one picture's base to the next
+  long long comp_at[3];       // a component's first row inside a picture
+  long long row_bytes[3], pitch[3]; // its rows: bytes of one, bytes from one to the next.  Tight rows are handed over as ONE row
+  int rows[3];                // of rows * row_bytes bytes; several rows: each starts on a 16-byte boundary (the layout's rule)
+  int word_bytes, shift;      // sample = (word >> shift) & mask, the word in the layout's byte order
+  unsigned mask;
+  int le;
   unsigned long long *sse;
 };
 void vc2_launch_squared_error(Launcher &L, const SseParams &p, int n_pictures, hipStream_t s);

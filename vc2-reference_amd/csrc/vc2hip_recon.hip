@@ -224,51 +224,72 @@ __device__ __forceinline__ u64 sq(unsigned a, unsigned b) {
   const unsigned d = a > b ? a - b : b - a;
   return (u64)d * d;
 }
-// the samples of one dword of each buffer (big-endian words of WB bytes, sample = word >> shift)
-template <int WB> __device__ __forceinline__ u64 sq_dword(unsigned x, unsigned y, int shift) {
-  if constexpr (WB == 4) return sq(__builtin_bswap32(x) >> shift, __builtin_bswap32(y) >> shift);
-  else if constexpr (WB == 2) {
-    const unsigned a = __builtin_bswap32(x), b = __builtin_bswap32(y);
-    return sq((a >> 16) >> shift, (b >> 16) >> shift) + sq((a & 0xFFFFu) >> shift, (b & 0xFFFFu) >> shift);
+// the samples of one dword of each buffer (words of WB bytes in the layout's byte order, sample = (word >> shift) & mask)
+template <int WB> __device__ __forceinline__ u64 sq_dword(unsigned x, unsigned y, int shift, unsigned mask, int le) {
+  if constexpr (WB == 4) {
+    const unsigned a = le ? x : __builtin_bswap32(x), b = le ? y : __builtin_bswap32(y);
+    return sq((a >> shift) & mask, (b >> shift) & mask);
+  } else if constexpr (WB == 2) { // (which word of the dword comes first does not matter to a sum)
+    const unsigned a = le ? x : __builtin_bswap32(x), b = le ? y : __builtin_bswap32(y);
+    return sq(((a >> 16) >> shift) & mask, ((b >> 16) >> shift) & mask) + sq(((a & 0xFFFFu) >> shift) & mask, ((b & 0xFFFFu) >> shift) & mask);
   } else {
     u64 s = 0;
 #pragma unroll
-    for (int k = 0; k < 32; k += 8) s += sq(((x >> k) & 0xFFu) >> shift, ((y >> k) & 0xFFu) >> shift);
+    for (int k = 0; k < 32; k += 8) s += sq((((x >> k) & 0xFFu) >> shift) & mask, (((y >> k) & 0xFFu) >> shift) & mask);
     return s;
   }
 }
-__device__ __forceinline__ u64 sq_sample(const uint8_t *a, const uint8_t *b, int wb, int shift) {
-  unsigned x = 0, y = 0;
-  for (int k = 0; k < wb; ++k) { x = (x << 8) | a[k]; y = (y << 8) | b[k]; }
-  return sq(x >> shift, y >> shift);
+__device__ __forceinline__ u64 sq_sample(const uint8_t *a, const uint8_t *b, int wb, int shift, unsigned mask, int le) {
+  return sq((vc2_load_word(a, wb, le) >> shift) & mask, (vc2_load_word(b, wb, le) >> shift) & mask);
 }
 // grid (blocks, pictures, 3).  The two buffers start on 16-byte boundaries and a component lies at the same offset in both,
 // so its whole 16-byte pieces are the same in both: lanes on consecutive pieces, the words before the first and behind the
 // last whole piece one by one.  WB == 0: word by word throughout (three-byte words, which no 16-byte piece holds whole).
+// A component is rows[comp] rows of row_bytes[comp] bytes, pitch[comp] apart (SseParams): one row for tight rows, else rows
+// that as a rule each start on a 16-byte boundary -- whole pieces first, over all rows, then the words behind each row's last piece.
 template <int WB>
 __global__ __launch_bounds__(256) void k_squared_error(const SseParams p) {
   __shared__ u64 part[4];
   const int pic = blockIdx.y, comp = blockIdx.z;
-  const long long at = (long long)pic * p.pic_bytes + p.comp_at[comp], end = at + p.comp_bytes[comp];
-  const long long first = (at + 15) & ~15ll, stop = end & ~15ll;
+  const long long at = (long long)pic * p.pic_bytes + p.comp_at[comp], end = at + p.row_bytes[comp];
+  const int rows = p.rows[comp];
   u64 acc = 0;
-  if (WB != 0 && first <= stop) {
+  if (rows > 1) {
+    const long long pitch = p.pitch[comp];
+    const int ppr = WB && !((at | pitch) & 15) ? (int)(p.row_bytes[comp] >> 4) : 0;        // whole pieces of a row (a packed picture stride
+                                                                                          // may leave a picture's rows off the boundary: words then)
+    const int wpr = (int)((p.row_bytes[comp] - 16ll * ppr) / p.word_bytes);              // words behind them
+    if constexpr (WB != 0)
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)rows * ppr; i += (long long)gridDim.x * 256) {
+      const int r = (int)(i / ppr), j = (int)(i - (long long)r * ppr);
+      const long long o = at + r * pitch + 16ll * j;
+      const uint4 x = *(const uint4 *)(p.a + o), y = *(const uint4 *)(p.b + o);
+      acc += sq_dword<WB>(x.x, y.x, p.shift, p.mask, p.le) + sq_dword<WB>(x.y, y.y, p.shift, p.mask, p.le) +
+             sq_dword<WB>(x.z, y.z, p.shift, p.mask, p.le) + sq_dword<WB>(x.w, y.w, p.shift, p.mask, p.le);
+    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)rows * wpr; i += (long long)gridDim.x * 256) {
+      const int r = (int)(i / wpr), j = (int)(i - (long long)r * wpr);
+      const long long o = at + r * pitch + 16ll * ppr + (long long)j * p.word_bytes;
+      acc += sq_sample(p.a + o, p.b + o, p.word_bytes, p.shift, p.mask, p.le);
+    }
+  } else if (const long long first = (at + 15) & ~15ll, stop = end & ~15ll; WB != 0 && first <= stop) {
     const long long pieces = (stop - first) >> 4;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pieces; i += (long long)gridDim.x * 256) {
       const uint4 x = *(const uint4 *)(p.a + first + 16 * i), y = *(const uint4 *)(p.b + first + 16 * i);
-      acc += sq_dword<WB>(x.x, y.x, p.shift) + sq_dword<WB>(x.y, y.y, p.shift) + sq_dword<WB>(x.z, y.z, p.shift) + sq_dword<WB>(x.w, y.w, p.shift);
+      acc += sq_dword<WB>(x.x, y.x, p.shift, p.mask, p.le) + sq_dword<WB>(x.y, y.y, p.shift, p.mask, p.le) +
+             sq_dword<WB>(x.z, y.z, p.shift, p.mask, p.le) + sq_dword<WB>(x.w, y.w, p.shift, p.mask, p.le);
     }
     if (blockIdx.x == 0) {
       const int head = (int)(first - at) / (WB ? WB : 1), tail = (int)(end - stop) / (WB ? WB : 1);
       for (int i = threadIdx.x; i < head + tail; i += 256) {
         const long long o = i < head ? at + (long long)i * WB : stop + (long long)(i - head) * WB;
-        acc += sq_sample(p.a + o, p.b + o, WB, p.shift);
+        acc += sq_sample(p.a + o, p.b + o, WB, p.shift, p.mask, p.le);
       }
     }
   } else {
-    const long long words = p.comp_bytes[comp] / p.word_bytes;
+    const long long words = p.row_bytes[comp] / p.word_bytes;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < words; i += (long long)gridDim.x * 256)
-      acc += sq_sample(p.a + at + i * p.word_bytes, p.b + at + i * p.word_bytes, p.word_bytes, p.shift);
+      acc += sq_sample(p.a + at + i * p.word_bytes, p.b + at + i * p.word_bytes, p.word_bytes, p.shift, p.mask, p.le);
   }
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
@@ -310,7 +331,7 @@ void vc2_launch_ld_check(Launcher &L, const LdEncParams &p, int n_pictures, hipS
 void vc2_launch_squared_error(Launcher &L, const SseParams &p, int n_pictures, hipStream_t s) {
   // enough workgroups per component to fill the GPU with a few pictures, few enough that a workgroup's one atomic is noise
   long long most = 0;
-  for (int c = 0; c < 3; ++c) most = p.comp_bytes[c] > most ? p.comp_bytes[c] : most;
+  for (int c = 0; c < 3; ++c) most = p.rows[c] * p.row_bytes[c] > most ? p.rows[c] * p.row_bytes[c] : most;
   long long bx = most / (16 * 256 * 8);
   bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
   const dim3 grid((unsigned)bx, (unsigned)n_pictures, 3);

@@ -52,6 +52,12 @@ class StreamParams(C.Structure):
                 ("end_of_sequence", C.c_int)]
 
 
+class SampleLayout(C.Structure):
+    """vc2hip_sample_layout: where and how the raw words of the device batch calls lie (include/vc2hip.h)"""
+    _fields_ = [("little_endian", C.c_int), ("lsb_justified", C.c_int), ("pitch", C.c_size_t * 3),
+                ("plane_offset", C.c_size_t * 3), ("picture_stride", C.c_size_t)]
+
+
 DWT_FAMILIES = ("tile", "fast", "stream", "pair", "plane")   # VC2HIP_DWT_TILE ... VC2HIP_DWT_PLANE
 
 
@@ -77,6 +83,7 @@ EXPORTS = [
     "vc2hip_picture_header", "vc2hip_stream_write_dev", "vc2hip_stream_read_dev",
     "vc2hip_encode_fields_batch_dev", "vc2hip_decode_fields_batch_dev", "vc2hip_decode_reduced_batch_dev",
     "vc2hip_encode_recon_batch_dev", "vc2hip_stream_write_fragments_dev",
+    "vc2hip_set_sample_layout", "vc2hip_layout_picture_bytes",
 ]
 
 
@@ -142,6 +149,9 @@ def load_library():
                                                     C.POINTER(CodingParams), C.c_int, vp]
     lib.vc2hip_encode_recon_batch_dev.argtypes = [vp, vp, C.c_int, C.POINTER(PictureFormat), C.POINTER(CodingParams),
                                                   vp, C.c_size_t, vp, vp, vp, vp]
+    lib.vc2hip_set_sample_layout.argtypes = [vp, C.POINTER(SampleLayout)]
+    lib.vc2hip_layout_picture_bytes.argtypes = [C.POINTER(PictureFormat), C.POINTER(SampleLayout)]
+    lib.vc2hip_layout_picture_bytes.restype = C.c_size_t
     lib.vc2hip_picture_header.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, u8p, C.c_size_t,
                                           C.POINTER(C.c_size_t)]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
@@ -179,6 +189,50 @@ def reduced_format(fmt, drop_levels):
     """the format of the pictures vc2hip_decode_reduced_batch_dev writes for coded pictures of fmt"""
     return PictureFormat(fmt.width >> drop_levels, fmt.height >> drop_levels, fmt.chroma_format, fmt.bit_depth, fmt.word_bytes,
                          fmt.chroma_bit_depth)
+
+
+def sample_layout(little_endian=False, lsb_justified=False, pitch=(0, 0, 0), plane_offset=(0, 0, 0), picture_stride=0):
+    """a vc2hip_sample_layout; the defaults are the file format (flags other than 0 / 1 are passed on for the library to refuse)"""
+    return SampleLayout(int(little_endian), int(lsb_justified), (C.c_size_t * 3)(*pitch), (C.c_size_t * 3)(*plane_offset),
+                        picture_stride)
+
+
+def layout_picture_bytes(lib, fmt, layout=None):
+    """vc2hip_layout_picture_bytes (host only): bytes from a picture's base to the end of its furthest plane row; 0: refused"""
+    return lib.vc2hip_layout_picture_bytes(C.byref(fmt), C.byref(layout) if layout is not None else None)
+
+
+def torch_planes(y, u, v):
+    """(base_pointer, layout) for pictures held as three torch tensors of shape (n, rows, cols) -- int16 / uint16 (two-byte
+    words) or uint8 -- that are views of ONE allocation, with unit stride in the last dimension and the same stride in the
+    first: little-endian LSB-justified words, the pitches, plane offsets and picture stride read from the tensors.  The base
+    is the lowest of the three data pointers.  ValueError for what no layout expresses."""
+    ts = (y, u, v)
+    if any(t.dim() != 3 for t in ts):
+        raise ValueError("torch_planes: every plane must have shape (n, rows, cols)")
+    if len({t.dtype for t in ts}) != 1 or len({t.device for t in ts}) != 1:
+        raise ValueError("torch_planes: the planes must share dtype and device")
+    wb = y.element_size()
+    if y.is_floating_point() or y.is_complex() or wb not in (1, 2):
+        raise ValueError("torch_planes: int16, uint16 or uint8 tensors")
+    if len({t.shape[0] for t in ts}) != 1:
+        raise ValueError("torch_planes: the planes must hold the same number of pictures")
+    n = y.shape[0]
+    if any(t.stride(2) != 1 for t in ts):
+        raise ValueError("torch_planes: unit stride in the last dimension (no layout steps over words)")
+    if any(t.stride(1) < t.shape[2] for t in ts):
+        raise ValueError("torch_planes: a row stride below the row")
+    if n > 1 and len({t.stride(0) for t in ts}) != 1:
+        raise ValueError("torch_planes: the planes must have the same stride in the first dimension")
+    base = min(t.data_ptr() for t in ts)
+    pitch = tuple(0 if t.stride(1) == t.shape[2] else t.stride(1) * wb for t in ts)   # (0: tight rows, whatever their bytes)
+    off = tuple(t.data_ptr() - base for t in ts)
+    stride = y.stride(0) * wb if n > 1 else 0
+    if base % 16 or any(x % 16 for x in pitch + off + (stride,)):
+        raise ValueError("torch_planes: base, pitches, plane offsets and picture stride must be multiples of 16 bytes")
+    if off == (0, 0, 0):
+        raise ValueError("torch_planes: the three planes start at the same address")
+    return base, sample_layout(True, True, pitch, off, stride)
 
 
 def coding_params(lib, fmt, kernel, depth, u, a, mode="HQ_ConstQ", q=0, s=0, prefix=0, scalar=1):
@@ -505,6 +559,13 @@ class Vc2Hip:
             for p in ins + outs:
                 self.lib.vc2hip_host_free(p)
         return res
+
+    def set_sample_layout(self, layout=None):
+        """the layout of every raw-sample buffer of the device batch calls from now on (None: the file format again)"""
+        self._chk(self.lib.vc2hip_set_sample_layout(self.h, C.byref(layout) if layout is not None else None))
+
+    def layout_picture_bytes(self, fmt, layout=None):
+        return layout_picture_bytes(self.lib, fmt, layout)
 
     def set_streams(self, k):
         self._chk(self.lib.vc2hip_set_streams(self.h, k))

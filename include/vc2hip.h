@@ -33,7 +33,27 @@ enum { VC2HIP_DD97 = 0, VC2HIP_LEGALL = 1, VC2HIP_DD137 = 2, VC2HIP_HAAR0 = 3,
 /* ColourFormat, src/Library/Picture.h:17 */
 enum { VC2HIP_CF444 = 0, VC2HIP_CF422 = 1, VC2HIP_CF420 = 2 };
 /* Mode, src/EncodeStream/EncodeParams.h */
-enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2 };
+enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2, VC2HIP_HQ_CAPPED = 3 };
+/* VC2HIP_HQ_CAPPED (an extension; the reference has no such mode): constant quality under a per-picture byte cap, on the
+ * encoding batch calls (vc2hip_encode_batch_dev, _fields_batch_dev, _recon_batch_dev and the host-buffer and _begin / _end
+ * calls that reach them).  vc2hip_coding_params is read as for HQ_CONSTQ except
+ *   q_index           the lowest index allowed -- the quality asked for; 0 .. VC2HIP_CAP_Q_TOP
+ *   compressed_bytes  the cap in bytes of ONE picture's slice payload (the unit of d_lens[i]; fields: of one field); >= 1
+ * Picture i of a batch gets one index q_i for all its slices: the smallest q in [q_index, 115] at which the HQ_CONSTQ
+ * encode of that picture succeeds (raises neither VC2HIP_ESCALAR nor VC2HIP_ECODE32) with a payload of at most
+ * compressed_bytes; if there is none, q_i = 115: the picture is coded there, without an error of its own, and the caller sees
+ * d_lens[i] > compressed_bytes (errors of the encode at 115 itself surface at vc2hip_sync as for HQ_CONSTQ).  Payload,
+ * d_lens, d_qidx, d_recon and d_sse are byte for byte those of the same call with mode HQ_CONSTQ and q_index = q_i on that
+ * picture alone; trying an index raises no error.  The indices are found on the device between the transform and the slice
+ * coder: the batch contract (asynchronous, no allocation / host copy / wait after the first call of a geometry, graph
+ * capture, vc2hip_set_streams, sample layouts, every context flag) holds unchanged.  Why 115: beyond it the reference's
+ * 32-bit quantisation factors wrap and a payload's length is no longer monotonic in the index.
+ * q_index outside 0 .. 115 or compressed_bytes < 1: VC2HIP_EINVAL, nothing launched.  Every call that does not encode
+ * (decoders, vc2hip_picture_header, the stream calls, vc2hip_max_payload_bytes) reads the mode as HQ_CONSTQ: the stream is
+ * a plain HQ VBR stream, and payload_stride >= vc2hip_max_payload_bytes as for HQ_CONSTQ.
+ * Not provided: a -m option of the command-line tools, rate control per slice inside a picture, LD
+ * (vc2hip_encode_picture_ld refuses every mode but VC2HIP_LD). */
+#define VC2HIP_CAP_Q_TOP 115
 
 enum {
   VC2HIP_OK = 0,
@@ -71,6 +91,7 @@ int vc2hip_create(int device, vc2hip_ctx **out);
 #define VC2HIP_FLAG_PLANES8_ALWAYS  0x400u /* decoder: one byte per band-plane coefficient from the first picture (default: once a batch has shown small coefficients) */
 #define VC2HIP_FLAG_PLANES8_NEVER   0x800u /* decoder: 16-bit band planes only */
 #define VC2HIP_FLAG_TWO_PASS_VBR    0x1000u /* VBR packing through slots + scan + compaction also where the one-pass slice coder is the default */
+#define VC2HIP_FLAG_CAP_GENERAL     0x2000u /* HQ_CAPPED: the general measuring kernel only (no register kernel) */
 int vc2hip_create_with_flags(int device, unsigned flags, vc2hip_ctx **out);
 /* same, but launch on a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) */
 int vc2hip_create_on_stream(int device, void *hip_stream, vc2hip_ctx **out);
@@ -177,7 +198,7 @@ typedef struct {
 typedef struct {
   int kernel, depth;      /* -k -d                                              */
   int y_slices, x_slices; /* from vc2hip_slice_size_is_valid                    */
-  int mode;               /* VC2HIP_HQ_CONSTQ / HQ_CBR / LD                     */
+  int mode;               /* VC2HIP_HQ_CONSTQ / HQ_CBR / LD / HQ_CAPPED         */
   int q_index;            /* ConstQ                                             */
   int compressed_bytes;   /* CBR / LD picture byte budget (-s)                  */
   int prefix, scalar;     /* -P -S                                              */
@@ -372,6 +393,8 @@ int vc2hip_decode_reduced_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size
  *               safe beyond one sample.  vc2hip_py.psnr_db turns a sum into the figure of -o PSNR
  *   d_qidx      n x y_slices * x_slices int32, raster order, or NULL: the index of every slice as the encoder used it --
  *               q_index everywhere for HQ_ConstQ, the result of the search for HQ_CBR and LD
+ *               (HQ_CAPPED: the picture's q_i in every slice of picture i, also with d_payload == NULL -- the
+ *               measurement runs whether or not a payload is written)
  * All modes, wavelets (Daub97 included), chroma formats, word_bytes 1 - 4, padded sizes, prefix and scalar; every context flag
  * gives the same bytes.  LD: the reconstruction is the DECODER's (DC-predicted LL band).  The reference's own -o Decoded
  * dequantises LD pictures without the prediction (EncodeStream.cpp:651); this call does not copy that.
@@ -400,6 +423,7 @@ int vc2hip_encode_recon_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
  *   top_field_first  1: the first field is rows 0, 2, 4, ... of every plane; 0: rows 1, 3, 5, ...
  *   cp          ONE FIELD picture: slices valid for the field heights (frame height / 2, frame chroma height / 2),
  *               compressed_bytes the field's budget (EncodeStream passes -s / 2).  cp is used as given: no budget arithmetic.
+ * VC2HIP_HQ_CAPPED: cp is one field's, as for every other mode, and the cap is per field.
  * Otherwise the batch calls' contract above, word for word: all modes, wavelets, chroma formats, word_bytes 1 - 4 and
  * chroma_bit_depth; 16-byte alignment; asynchronous on the ctx stream, errors at vc2hip_sync; vc2hip_set_streams splits by
  * whole frames (lane i: frames [first, first + count), slots [2 first, 2 (first + count))), results identical.

@@ -132,6 +132,7 @@ enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS,
        B_FRAGS, B_FRAGPIC, B_FRAGJUMP, // stream_write_fragments_dev: fragment tables, per-picture results, the cut's workspace
        B_RSTORE, B_RSTOREW, // encode_recon_batch_dev: the quantised coefficients in the decoder's layout
        B_PLANE_QM,          // plane_inverse: the quantisation matrix of plane_qm_key
+       B_CAPTAB,            // HQ_CAPPED: the per-picture length table (vc2hip_cap.h)
        B_COUNT };
 
 struct vc2hip_ctx {
@@ -188,6 +189,7 @@ struct vc2hip_ctx {
   bool allow_stream = true;   // VC2HIP_NO_STREAM=1: tile kernels instead of the streaming level kernels (tests, A/B)
   bool allow_pair = true;     // VC2HIP_FLAG_NO_PAIR: one launch per transform level (vc2hip_dwt_pair.hip off; tests, A/B)
   bool cbr_general = false;   // VC2HIP_FLAG_CBR_GENERAL: the HQ_CBR search without the register kernels
+  bool cap_general = false;   // VC2HIP_FLAG_CAP_GENERAL: the HQ_CAPPED measurement without the register kernel
   bool ld_diagonals = false;  // VC2HIP_FLAG_LD_DIAGONALS: the LD index search with one launch per slice anti-diagonal
   unsigned flags = 0;
   // vc2hip_set_streams(k > 1): device-resident batches are cut into k contiguous sub-batches, each on its own
@@ -368,7 +370,7 @@ static int create_common(int device, hipStream_t stream, bool own, vc2hip_ctx **
       {"VC2HIP_STORE32", VC2HIP_FLAG_STORE32}, {"VC2HIP_NO_STREAM", VC2HIP_FLAG_NO_STREAM}, {"VC2HIP_NO_PAIR", VC2HIP_FLAG_NO_PAIR},
       {"VC2HIP_NO_BANDPLANES", VC2HIP_FLAG_NO_BANDPLANES}, {"VC2HIP_NO_HEADS", VC2HIP_FLAG_NO_HEADS},
       {"VC2HIP_NO_CBR_INDEX", VC2HIP_FLAG_NO_CBR_INDEX}, {"VC2HIP_GENERIC_DWT", VC2HIP_FLAG_GENERIC_DWT},
-      {"VC2HIP_SINGLE_PASS_VBR", VC2HIP_FLAG_SINGLE_PASS_VBR}, {"VC2HIP_TWO_PASS_VBR", VC2HIP_FLAG_TWO_PASS_VBR}, {"VC2HIP_CBR_GENERAL", VC2HIP_FLAG_CBR_GENERAL},
+      {"VC2HIP_SINGLE_PASS_VBR", VC2HIP_FLAG_SINGLE_PASS_VBR}, {"VC2HIP_TWO_PASS_VBR", VC2HIP_FLAG_TWO_PASS_VBR}, {"VC2HIP_CBR_GENERAL", VC2HIP_FLAG_CBR_GENERAL}, {"VC2HIP_CAP_GENERAL", VC2HIP_FLAG_CAP_GENERAL},
       {"VC2HIP_PLANES8_ALWAYS", VC2HIP_FLAG_PLANES8_ALWAYS}, {"VC2HIP_PLANES8_NEVER", VC2HIP_FLAG_PLANES8_NEVER}};
     for (const auto &e : env) { const char *v = getenv(e.name); if (v && v[0] == '1') flags |= e.flag; }
     { const char *v = getenv("VC2HIP_LD_ROWS"); if (v && v[0] == '0') flags |= VC2HIP_FLAG_LD_DIAGONALS; }
@@ -386,6 +388,7 @@ static int create_common(int device, hipStream_t stream, bool own, vc2hip_ctx **
   c->two_pass_vbr = !(flags & VC2HIP_FLAG_SINGLE_PASS_VBR);
   c->force_two_pass_vbr = (flags & VC2HIP_FLAG_TWO_PASS_VBR) != 0;
   c->cbr_general = (flags & VC2HIP_FLAG_CBR_GENERAL) != 0;
+  c->cap_general = (flags & VC2HIP_FLAG_CAP_GENERAL) != 0;
   c->ld_diagonals = (flags & VC2HIP_FLAG_LD_DIAGONALS) != 0;
   c->flags = flags;
   if (hipSetDevice(device) != hipSuccess) { delete c; return VC2HIP_EHIP; }
@@ -806,7 +809,7 @@ static size_t max_slice_bytes(int prefix, int scalar) { return (size_t)prefix + 
 extern "C" size_t vc2hip_max_payload_bytes(const vc2hip_picture_format *f, const vc2hip_coding_params *cp) {
   (void)f;
   const size_t n = (size_t)cp->y_slices * cp->x_slices;
-  if (cp->mode == VC2HIP_HQ_CONSTQ) return n * max_slice_bytes(cp->prefix, cp->scalar);
+  if (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CAPPED) return n * max_slice_bytes(cp->prefix, cp->scalar);
   if (cp->mode == VC2HIP_HQ_CBR) return (size_t)cp->compressed_bytes + n * (cp->prefix + (size_t)cp->scalar + 4);
   return (size_t)cp->compressed_bytes + n;
 }
@@ -1918,7 +1921,9 @@ extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, i
 static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int top_first, int n, const vc2hip_picture_format *f,
                                const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
                                const ReconOut *ro) {
-  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD) return set_err(c, VC2HIP_EINVAL);
+  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD && cp->mode != VC2HIP_HQ_CAPPED) return set_err(c, VC2HIP_EINVAL);
+  if (cp->mode == VC2HIP_HQ_CAPPED && (cp->q_index < 0 || cp->q_index > VC2_CAP_Q_TOP || cp->compressed_bytes < 1))
+    return set_err(c, VC2HIP_EINVAL, "HQ_CAPPED: q_index 0 .. 115, compressed_bytes >= 1");
   if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
   if (cp->mode != VC2HIP_LD && (cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
   Geom g;
@@ -1997,6 +2002,22 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
     for (int b = 0; b < 3 * g.depth + 1; ++b) p.qmatrix[b] = qm[b];
     p.n_bands = 3 * g.depth + 1;
     vc2_launch_cbr(c->L, p, n, c->stream);
+  } else if (cp->mode == VC2HIP_HQ_CAPPED) { // one index per picture, found on the device (vc2hip_cap.h)
+    if (d_payload && payload_stride < vc2hip_max_payload_bytes(f, cp)) return set_err(c, VC2HIP_ECAP);
+    CapParams p;
+    memset(&p, 0, sizeof p);
+    NEED(c, B_CAPTAB, (size_t)n * VC2_CAP_ROW * 8, p.table);
+    HIPCHK(c, hipMemsetAsync(p.table, 0, (size_t)n * VC2_CAP_ROW * 8, c->stream));
+    p.s.store = d_store; p.s.store_stride = (long long)ns * g.slice_coefs; p.s.qidx = d_q;
+    p.s.store16 = s16; p.s.store_wide = d_storew;
+    p.s.n_slices = ns; p.s.slice_coefs = g.slice_coefs;
+    fill_comp_arrays(g, p.s.comp_n, p.s.comp_off, p.s.comp_n0);
+    p.s.scalar = cp->scalar; p.s.err = c->d_err;
+    p.s.general_only = c->cap_general;
+    for (int b = 0; b < 3 * g.depth + 1; ++b) p.s.qmatrix[b] = qm[b];
+    p.s.n_bands = 3 * g.depth + 1;
+    p.prefix = cp->prefix; p.floor = cp->q_index; p.cap = (unsigned long long)cp->compressed_bytes;
+    vc2_launch_cap(c->L, p, n, c->stream);
   } else {
     if (d_payload && payload_stride < vc2hip_max_payload_bytes(f, cp)) return set_err(c, VC2HIP_ECAP);
     // quantIndicesConstQ, EncodeStream.cpp:128-138
@@ -2324,7 +2345,7 @@ struct HeaderBits { // MSB-first writer of DataUnit.cpp's BitWriter
 bool stream_cp_ok(const vc2hip_coding_params *cp) {
   if (!cp || cp->kernel < 0 || cp->kernel > 6 || cp->depth < 0 || cp->y_slices < 1 || cp->x_slices < 1) return false;
   if (cp->mode == VC2HIP_LD) return cp->compressed_bytes > 0;
-  return (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CBR) && cp->prefix >= 0 && cp->scalar >= 1;
+  return (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CBR || cp->mode == VC2HIP_HQ_CAPPED) && cp->prefix >= 0 && cp->scalar >= 1;
 }
 // what the transform parameters carry after the slice counts: prefix, scalar (HQ) or the slice-bytes fraction in lowest
 // terms (LD: utils::rationalise(pictureBytes, slices), EncodeStream.cpp:263)

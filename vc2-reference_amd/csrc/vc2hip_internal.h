@@ -328,6 +328,26 @@ struct CbrParams {
 };
 #define VC2_CBR_MARK 0x7FFFFFFF
 
+// HQ_CAPPED (vc2hip_cap.h): one index per picture, the smallest of floor .. VC2_CAP_Q_TOP whose
+// ConstQ payload is at most cap bytes.  Two rounds of measure + pick over a per-picture table of VC2_CAP_ROW u64 words:
+//   [0 .. 14]  round 1: the picture's payload bytes at floor + 8 k (a candidate that cannot be coded: >= VC2_CAP_NOFIT)
+//   [16 .. 22] round 2: the same at base + 1 + j, j < count
+//   [24] base, [25] count, [26] the index if none of round 2 fits (written by the first pick)
+#define VC2_CAP_Q_TOP 115
+#define VC2_CAP_ROW 32
+#define VC2_CAP_R2 16
+#define VC2_CAP_BASE 24
+#define VC2_CAP_COUNT 25
+#define VC2_CAP_ELSE 26
+#define VC2_CAP_NOFIT (1ull << 40)
+struct CapParams {
+  CbrParams s;                // store, geometry, matrix as the HQ_CBR search has them; qidx: the marks of the handed-back slices, then the result
+  unsigned long long *table;  // n_pictures * VC2_CAP_ROW, zero before the first round
+  unsigned long long cap;
+  int prefix, floor;
+  int round;                  // 0 / 1
+};
+
 // ------------------------------------------------------------------------------------------
 // launchers (implemented in the kernel TUs)
 // ------------------------------------------------------------------------------------------
@@ -363,6 +383,7 @@ void vc2_launch_compact(Launcher &L, const uint8_t *slots, int slot_bytes, const
                         const uint32_t *offsets, uint8_t *payload, long long payload_stride,
                         int n_slices, int n_pictures, hipStream_t s);
 void vc2_launch_cbr(Launcher &L, const CbrParams &p, int n_pictures, hipStream_t s);
+void vc2_launch_cap(Launcher &L, const CapParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_unpack(Launcher &L, const UnpackParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_cbr_index(Launcher &L, const uint8_t *payload, long long stride, const unsigned long long *lens, const int32_t *budget,
                           const uint32_t *cbr_offs, unsigned long long total, uint32_t *offsets, int n_slices, int prefix, int scalar,

@@ -1500,6 +1500,7 @@ __global__ __launch_bounds__(256) void k_cbr_search_reg(const CbrParams p) {
 }
 
 #include "vc2hip_cbr16.h"
+#include "vc2hip_cap.h"
 
 // wavefronts per workgroup so that their LDS (per_wave bytes each) fits: 4 down to 1; 0 if even one does not
 int vc2_waves_for_lds(size_t per_wave);

@@ -1279,7 +1279,9 @@ __global__ __launch_bounds__(256) void k_cbr_search(const CbrParams p) {
     return wave_sum64(acc);
   };
 
-  bool bad = false;
+  // bad: a length byte overflowed at a trial (comp_bytes has set VC2_DEVERR_SCALAR: the reference's "Slice scalar is too
+  // small" -- and nothing else: the host reports the quantiser index error first); bad_q: the refinement left the table
+  bool bad = false, bad_q = false;
   int trial = 63, q = 127, delta = 64;
   while (delta > 0) {
     delta >>= 1;
@@ -1291,18 +1293,18 @@ __global__ __launch_bounds__(256) void k_cbr_search(const CbrParams p) {
   }
   if (!bad) {
     trial = q;
-    long long prev = yss(trial, bad), d;
+    long long prev = yss(trial, bad_q), d;
     do {
       ++trial;
-      const long long cur = yss(trial, bad);
-      bad = __any(bad);
-      if (bad) break;
+      const long long cur = yss(trial, bad_q);
+      bad_q = __any(bad_q);
+      if (bad_q) break;
       d = cur - prev;
       prev = cur;
     } while (d < 0);
     q = trial - 1;
   }
-  if (__any(bad) && lane == 0) atomicOr(p.err, VC2_DEVERR_QINDEX);
+  if (__any(bad_q) && lane == 0) atomicOr(p.err, VC2_DEVERR_QINDEX);
   if (lane == 0) p.qidx[(size_t)pic * p.n_slices + slice] = q;
   wave_lds_sync();
   }; // search(slice)

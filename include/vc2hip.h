@@ -326,7 +326,8 @@ int vc2hip_set_streams(vc2hip_ctx *ctx, int k);
  * vc2hip_layout_picture_bytes; a plane beyond the kernels' 32-bit row offsets: a pitch of 2^23 bytes or more, or rows *
  * pitch of 2^31 bytes or more (the kernels form a row's offset as a 24-bit by 24-bit product of the row and the pitch in
  * 16-bit words, plus the column, in 32 bits).
- * Not covered: interleaved chroma (P210 / NV16-style UV pairs) and packed formats (v210).
+ * Not covered by a layout: interleaved chroma (P210 / NV16-style UV pairs) and packed formats (v210) -- see
+ * vc2hip_set_packed_format below.
  * Extension, no counterpart in the reference. */
 typedef struct {
   int little_endian;        /* 0: big-endian words (the file format); 1: little-endian */
@@ -343,6 +344,62 @@ int vc2hip_set_sample_layout(vc2hip_ctx *ctx, const vc2hip_sample_layout *layout
 /* Host arithmetic: bytes from a picture's base to the end of its furthest plane row.  NULL or an all-zero layout:
  * vc2hip_raw_picture_bytes(fmt); 0 for a layout the calls would refuse for pictures of fmt. */
 size_t vc2hip_layout_picture_bytes(const vc2hip_picture_format *fmt, const vc2hip_sample_layout *layout);
+/* Packed and semi-planar pictures: the two forms in which broadcast video reaches a GPU and which no sample layout expresses.
+ *   VC2HIP_PACKING_V210        the SDI / ST 2110 capture format of 4:2:2 10-bit: groups of 6 pixels in 16 bytes, four
+ *                              little-endian 32-bit words of three 10-bit fields at bits 0, 10 and 20:
+ *                                w0 = Cb0 | Y0 << 10 | Cr0 << 20     w1 = Y1 | Cb1 << 10 | Y2 << 20
+ *                                w2 = Cr1 | Y3 << 10 | Cb2 << 20     w3 = Y4 | Cr2 << 10 | Y5 << 20
+ *                              A row is ceil(width / 6) groups; the tight pitch is that many x 16 bytes (the conventional
+ *                              128-byte alignment is the caller's pitch).  Needs 4:2:2, bit_depth 10, chroma_bit_depth 0 or
+ *                              10, word_bytes 2 and an even width (not a multiple of 6: 1280 is none).
+ *                              Read: bits 30 - 31 of every word are ignored, and the fields of a row's last group beyond its
+ *                              width.  Written: those bits and fields are zero, every group of a row is written whole, and
+ *                              nothing else is touched (row tails up to the pitch, bytes between pictures).
+ *   VC2HIP_PACKING_SEMIPLANAR  a Y plane as under a sample layout and ONE plane of U, V word pairs (U first): 2 x chroma
+ *                              width words per row, chroma height rows.  4:2:0, 4:2:2 and 4:4:4 with word_bytes 1 or 2:
+ *                              NV12 / NV16 / NV24 at 8 bits; P010 / P210 / P016 / P216 are little_endian = 1,
+ *                              lsb_justified = 0.  chroma_bit_depth is honoured as the planar path honours it.
+ *                              Read: the bits of a word outside the sample are ignored.  Written: they are zero, and
+ *                              nothing outside the rows of the two planes is touched.
+ *   little_endian, lsb_justified   SEMIPLANAR: as in vc2hip_sample_layout.  V210: must be 0 (the format fixes both)
+ *   pitch[0], [1]      bytes between the v210 rows / the Y rows, and between the UV rows (V210: [1] must be 0); 0 = tight
+ *   plane_offset[0], [1]   SEMIPLANAR: bytes from a picture's base to its Y and UV plane; both 0 = the UV plane behind Y's
+ *                      last pitch-spaced row.  V210: must be 0
+ *   picture_stride     bytes from one picture's base to the next; 0 = packed: vc2hip_packed_picture_bytes
+ * The format is context state exactly as the sample layout is: pure host state, set between any two calls, kept by a captured
+ * call, used by the lanes of vc2hip_set_streams (which cut the batch at the packed picture stride).  While one is set it
+ * describes EVERY raw-sample buffer of every device batch call -- d_raw, d_raw_out, d_recon (the overlap refusal uses the
+ * packed extents), d_frames / d_frames_out (the format is the FRAME's; the field addressing goes on top) and the output of
+ * vc2hip_decode_reduced_batch_dev (the format describes the REDUCED pictures) -- and the context's sample layout is kept but
+ * not used; NULL or packing VC2HIP_PACKING_NONE brings it back.  The host-buffer and pipelined picture calls, the
+ * fine-grained int32 calls, the stream calls and the CLI tools keep the file format.
+ * The packing changes where samples lie, not what they are: payload bytes, lengths, d_qidx, d_sse and decoded sample values
+ * are those of the same pictures in the file format, and vc2hip_dwt_launches shows the record of the same call on planar
+ * little-endian LSB-justified pictures.  The pictures pass through a planar staging buffer of the context (small
+ * bandwidth-bound kernels on the call's stream, vc2hip_profile_* names v210_unpack, v210_pack, uv_deinterleave,
+ * uv_interleave); the batch contract holds word for word: asynchronous, nothing allocated, copied to the host or waited for
+ * after the first call of a geometry and n, a caller's stream, graph capture after a warm-up, lanes as parallel branches.
+ * VC2HIP_EINVAL -- from the setter for what the struct alone shows, from the batch call where fmt is needed; nothing is
+ * launched, no output byte is touched and the context keeps the format it had: an unknown packing; flags other than 0 / 1;
+ * V210 fields that must be 0; a non-zero pitch, offset or stride that is not a multiple of 16 bytes; a pitch below the row; a
+ * stride below vc2hip_packed_picture_bytes; a pitch of 2^23 bytes or more, or rows * pitch of 2^31 bytes or more; a fmt the
+ * packing does not admit (above; SEMIPLANAR: word_bytes 3 or 4); for the reduced call, a reduced width V210 does not admit;
+ * while vc2hip_set_streams(k > 1) is in force, a picture stride that is not a multiple of 16 bytes (tight semi-planar pictures
+ * of odd sizes at one-byte words: the lanes cut the batch at the stride, and every lane's base keeps the 16-byte rule).
+ * Not provided: V-first chroma order (NV21 / NV61), UYVY / YUY2, RGB, and options of the command-line tools.
+ * Extension, no counterpart in the reference. */
+enum { VC2HIP_PACKING_NONE = 0, VC2HIP_PACKING_V210 = 1, VC2HIP_PACKING_SEMIPLANAR = 2 };
+typedef struct {
+  int packing;                      /* VC2HIP_PACKING_* */
+  int little_endian, lsb_justified; /* SEMIPLANAR, as in vc2hip_sample_layout; V210: must be 0 (the format fixes both) */
+  size_t pitch[2];                  /* [0]: v210 rows / Y rows, [1]: UV rows (V210: must be 0); 0 = tight */
+  size_t plane_offset[2];           /* SEMIPLANAR: Y, UV; both 0 = UV behind Y's last pitch-spaced row; V210: must be 0 */
+  size_t picture_stride;            /* 0 = packed: vc2hip_packed_picture_bytes */
+} vc2hip_packed_format;
+int vc2hip_set_packed_format(vc2hip_ctx *ctx, const vc2hip_packed_format *pf); /* NULL or packing NONE: off */
+/* Host arithmetic: bytes from a picture's base to the end of its furthest row under pf; 0 for what the calls refuse for
+ * pictures of fmt (a NULL pf or packing NONE included: that is no packed format). */
+size_t vc2hip_packed_picture_bytes(const vc2hip_picture_format *fmt, const vc2hip_packed_format *pf);
 int vc2hip_encode_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
                             const vc2hip_picture_format *fmt, const vc2hip_coding_params *cp,
                             void *d_payload, size_t payload_stride, uint64_t *d_lens);

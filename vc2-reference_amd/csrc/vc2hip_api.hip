@@ -133,6 +133,7 @@ enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS,
        B_RSTORE, B_RSTOREW, // encode_recon_batch_dev: the quantised coefficients in the decoder's layout
        B_PLANE_QM,          // plane_inverse: the quantisation matrix of plane_qm_key
        B_CAPTAB,            // HQ_CAPPED: the per-picture length table (vc2hip_cap.h)
+       B_PKIN, B_PKOUT,     // vc2hip_set_packed_format: the planar staging of a call's input and of its output pictures
        B_COUNT };
 
 struct vc2hip_ctx {
@@ -219,6 +220,9 @@ struct vc2hip_ctx {
   // the file format).  layout_bypass: a host-buffer picture call is running its batch call on the context -- file format.
   vc2hip_sample_layout layout = {};
   bool has_layout = false, layout_bypass = false;
+  // vc2hip_set_packed_format: v210 or semi-planar pictures (pure host state as the layout; while set the layout is not used)
+  vc2hip_packed_format packed = {};
+  bool has_packed = false;
 };
 
 static const char *code_text(int code) {
@@ -566,6 +570,7 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
     vc2hip_ctx *l = c->lanes[i];
     c->in_split = (i == 0);
     l->layout = c->layout; l->has_layout = c->has_layout; // (host state: a lane's pictures lie as the context's)
+    l->packed = c->packed; l->has_packed = c->has_packed;
     const int r = fn(l, first[i], count[i]);
     c->in_split = false;
     if (r && !rc) rc = i ? set_err(c, r, l->err.c_str()) : r;
@@ -775,9 +780,91 @@ static bool format_ok(const vc2hip_picture_format *f) {
 }
 // the layout of the context's device batch calls: null = the file format
 static const vc2hip_sample_layout *active_layout(const vc2hip_ctx *c) { return c->has_layout && !c->layout_bypass ? &c->layout : nullptr; }
-// ... resolved for a buffer of pictures of format f; VC2HIP_EINVAL (nothing launched) where the check needs the format
+
+// Packed and semi-planar pictures (vc2hip_set_packed_format), resolved against the pictures of a buffer.
+// Plane 0: the v210 rows / the Y plane; plane 1: the UV plane (SEMIPLANAR only).
+struct PackedLayout {
+  int packing, le, lsb;
+  int rows[2];
+  size_t row[2], pitch[2], at[2]; // bytes of a row; from row to row; from a picture's base to the plane
+  size_t extent, stride;
+};
+static const char *packed_struct_error(const vc2hip_packed_format *p) {
+  if (!p || p->packing == VC2HIP_PACKING_NONE) return nullptr;
+  if (p->packing != VC2HIP_PACKING_V210 && p->packing != VC2HIP_PACKING_SEMIPLANAR) return "packed format: unknown packing";
+  if ((p->little_endian != 0 && p->little_endian != 1) || (p->lsb_justified != 0 && p->lsb_justified != 1))
+    return "packed format: little_endian and lsb_justified must be 0 or 1";
+  if (p->packing == VC2HIP_PACKING_V210 && (p->little_endian || p->lsb_justified || p->pitch[1] || p->plane_offset[0] || p->plane_offset[1]))
+    return "packed format: v210 fixes byte order and justification and has one plane (those fields must be 0)";
+  if ((p->pitch[0] | p->pitch[1] | p->plane_offset[0] | p->plane_offset[1] | p->picture_stride) & 15)
+    return "packed format: pitches, plane offsets and the picture stride must be multiples of 16 bytes";
+  return nullptr;
+}
+// f: the format of the buffer's pictures (frames for the field calls, the reduced pictures for the reduced call)
+static const char *resolve_packed(const vc2hip_picture_format *f, const vc2hip_packed_format *p, PackedLayout &r) {
+  if (!p || p->packing == VC2HIP_PACKING_NONE) return "packed format: none";
+  if (const char *e = packed_struct_error(p)) return e;
+  int ch, cw;
+  chroma_dims(f->height, f->width, f->chroma_format, &ch, &cw);
+  memset(&r, 0, sizeof r);
+  r.packing = p->packing; r.le = p->little_endian; r.lsb = p->lsb_justified;
+  int planes;
+  if (p->packing == VC2HIP_PACKING_V210) {
+    if (f->chroma_format != VC2HIP_CF422 || f->bit_depth != 10 || (f->chroma_bit_depth != 0 && f->chroma_bit_depth != 10) ||
+        f->word_bytes != 2 || f->width % 2)
+      return "packed format: v210 needs 4:2:2, bit_depth 10, chroma_bit_depth 0 or 10, word_bytes 2 and an even width";
+    planes = 1;
+    r.rows[0] = f->height; r.row[0] = (size_t)((f->width + 5) / 6) * 16;
+  } else {
+    if (f->word_bytes != 1 && f->word_bytes != 2) return "packed format: semi-planar pictures have word_bytes 1 or 2";
+    planes = 2;
+    r.rows[0] = f->height; r.row[0] = (size_t)f->width * f->word_bytes;
+    r.rows[1] = ch; r.row[1] = 2 * (size_t)cw * f->word_bytes;
+  }
+  const bool placed = (p->plane_offset[0] | p->plane_offset[1]) != 0;
+  for (int k = 0; k < planes; ++k) {
+    r.pitch[k] = p->pitch[k] ? p->pitch[k] : r.row[k];
+    if (r.pitch[k] < r.row[k]) return "packed format: a pitch below the row's bytes";
+    if (r.pitch[k] >= VC2_LAYOUT_MAX_PITCH || (size_t)r.rows[k] * r.pitch[k] >= VC2_LAYOUT_MAX_PLANE)
+      return "packed format: a plane beyond the kernels' 32-bit row offsets (pitch below 2^23 bytes, rows * pitch below 2^31)";
+    r.at[k] = placed ? p->plane_offset[k] : k ? r.at[0] + (size_t)r.rows[0] * r.pitch[0] : 0;
+    const size_t end = r.rows[k] ? r.at[k] + (size_t)(r.rows[k] - 1) * r.pitch[k] + r.row[k] : r.at[k];
+    if (end > r.extent) r.extent = end;
+  }
+  r.stride = p->picture_stride ? p->picture_stride : r.extent;
+  if (r.stride < r.extent) return "packed format: a picture stride below vc2hip_packed_picture_bytes";
+  return nullptr;
+}
+static const vc2hip_packed_format *active_packed(const vc2hip_ctx *c) { return c->has_packed && !c->layout_bypass ? &c->packed : nullptr; }
+
+extern "C" int vc2hip_set_packed_format(vc2hip_ctx *c, const vc2hip_packed_format *p) {
+  if (!c) return VC2HIP_EINVAL;
+  if (const char *e = packed_struct_error(p)) return set_err(c, VC2HIP_EINVAL, e);
+  c->has_packed = p && p->packing != VC2HIP_PACKING_NONE;
+  if (c->has_packed) c->packed = *p;
+  return VC2HIP_OK;
+}
+extern "C" size_t vc2hip_packed_picture_bytes(const vc2hip_picture_format *f, const vc2hip_packed_format *p) {
+  PackedLayout r;
+  if (!format_ok(f) || resolve_packed(f, p, r)) return 0;
+  return r.extent;
+}
+
+// ... resolved for a buffer of pictures of format f; VC2HIP_EINVAL (nothing launched) where the check needs the format.
+// Under a packed format: that format's extent and stride (the planes are the staging's: raw_view)
 static int batch_layout(vc2hip_ctx *c, const vc2hip_picture_format *f, RawLayout &r) {
   if (!format_ok(f)) return set_err(c, VC2HIP_EINVAL);
+  if (const vc2hip_packed_format *pf = active_packed(c)) {
+    PackedLayout pl;
+    if (const char *e = resolve_packed(f, pf, pl)) return set_err(c, VC2HIP_EINVAL, e);
+    // (lanes cut the batch at the picture stride and every lane's base keeps the 16-byte rule: refused here, before lane 0
+    // is enqueued, not by lane 1's own entry check)
+    if (c->lanes.size() > 1 && !c->in_split && (pl.stride & 15))
+      return set_err(c, VC2HIP_EINVAL, "packed format: with vc2hip_set_streams(k > 1) the picture stride must be a multiple of 16 bytes");
+    memset(&r, 0, sizeof r);
+    r.le = pl.le; r.lsb = pl.lsb; r.extent = pl.extent; r.stride = pl.stride;
+    return VC2HIP_OK;
+  }
   if (const char *e = resolve_layout(f, active_layout(c), r)) return set_err(c, VC2HIP_EINVAL, e);
   return VC2HIP_OK;
 }
@@ -1743,6 +1830,72 @@ static void raw_planes(const vc2hip_picture_format *f, const vc2hip_sample_layou
   }
 }
 
+// Where the transform's edge kernels find the raw words of one caller buffer: the buffer itself under the context's sample
+// layout, or -- under a packed format -- the context's planar staging of it (semi-planar: the Y plane stays in the caller's
+// buffer, only the chroma is staged).  An input is unpacked into the staging before the first launch reads it, an output
+// packed from it behind the last launch that writes it (view_convert), on the context's stream.
+struct RawView {
+  const vc2hip_sample_layout *lay; // planar: the caller's layout (null: the file format) ...
+  const void *base;                // ... of this buffer
+  bool packed;
+  PackedLayout pl;                 // packed: the caller's buffer
+  uint8_t *stage;                  // the staging (null with a null buffer: planning only)
+  size_t spitch[3], sat[3], sstride; // its rows, planes and pictures (semi-planar: [0] unused)
+  int word_bytes, width, n;        // of the buffer's pictures
+};
+// fb: the format of the buffer's pictures (frames for the field calls), nbuf of them; which: B_PKIN / B_PKOUT
+static int raw_view(vc2hip_ctx *c, const vc2hip_picture_format *fb, int nbuf, const void *base, int which, RawView &v) {
+  memset(&v, 0, sizeof v);
+  v.base = base;
+  const vc2hip_packed_format *pf = active_packed(c);
+  if (!pf) { v.lay = active_layout(c); return VC2HIP_OK; }
+  if (const char *e = resolve_packed(fb, pf, v.pl)) return set_err(c, VC2HIP_EINVAL, e); // (refused at the entry points already)
+  v.packed = true;
+  v.word_bytes = fb->word_bytes; v.width = fb->width; v.n = nbuf;
+  int ch, cw;
+  chroma_dims(fb->height, fb->width, fb->chroma_format, &ch, &cw);
+  const size_t py = ((size_t)fb->width * fb->word_bytes + 15) & ~(size_t)15, pc = ((size_t)cw * fb->word_bytes + 15) & ~(size_t)15;
+  const bool y_staged = v.pl.packing == VC2HIP_PACKING_V210;
+  v.spitch[0] = py; v.spitch[1] = v.spitch[2] = pc;
+  v.sat[0] = 0; v.sat[1] = y_staged ? (size_t)fb->height * py : 0; v.sat[2] = v.sat[1] + (size_t)ch * pc;
+  v.sstride = v.sat[2] + (size_t)ch * pc;
+  if (base) NEED(c, which, (size_t)nbuf * v.sstride + 16, v.stage);
+  return VC2HIP_OK;
+}
+// raw_planes for a view; f: the PICTURES' format (a field's, for fields == 2)
+static void view_planes(const RawView &v, const vc2hip_picture_format *f, int fields, int top_first, const void *pl[3], RawPlane rl[3]) {
+  if (!v.packed) { raw_planes(f, v.lay, v.base, fields, top_first, pl, rl); return; }
+  const bool v210 = v.pl.packing == VC2HIP_PACKING_V210;
+  for (int k = 0; k < 3; ++k) {
+    const bool in_place = !v210 && k == 0; // (the Y plane of a semi-planar picture: plane 0 of a layout in the caller's word form)
+    const uint8_t *at = in_place ? (const uint8_t *)v.base + v.pl.at[0] : v.stage + v.sat[k];
+    const size_t pitch = in_place ? v.pl.pitch[0] : v.spitch[k];
+    const bool second_first = fields == 2 && !top_first;
+    pl[k] = at + (second_first ? pitch : 0);
+    rl[k].stride = (long long)(in_place ? v.pl.stride : v.sstride);
+    rl[k].pitch = fields * (int)pitch;
+    rl[k].field_step = fields == 2 ? (top_first ? (int)pitch : -(int)pitch) : 0;
+    rl[k].field_shift = fields == 2;
+    rl[k].le = v210 ? 1 : v.pl.le; rl[k].lsb = v210 ? 1 : v.pl.lsb;
+  }
+}
+// pack: the staging -> the caller's buffer (an output); else the caller's buffer -> the staging (an input)
+static void view_convert(vc2hip_ctx *c, const RawView &v, bool pack) {
+  if (!v.packed || !v.stage) return;
+  const bool v210 = v.pl.packing == VC2HIP_PACKING_V210;
+  const int k = v210 ? 0 : 1; // the caller's plane the kernels convert
+  PackedParams p;
+  memset(&p, 0, sizeof p);
+  p.packed = (uint8_t *)v.base + v.pl.at[k]; p.packed_stride = (long long)v.pl.stride; p.packed_pitch = (int)v.pl.pitch[k];
+  for (int q = 0; q < 3; ++q) { p.plane[q] = v.stage + v.sat[q]; p.plane_pitch[q] = (int)v.spitch[q]; }
+  p.plane_stride = (long long)v.sstride;
+  p.rows = v.pl.rows[k];
+  p.width = v210 ? v.width : (int)(v.pl.row[1] / (2 * (size_t)v.word_bytes));
+  p.v210 = v210; p.word_bytes = v.word_bytes;
+  p.vec = !(((size_t)v.base | v.pl.at[k] | v.pl.stride | v.pl.pitch[k]) & 15);
+  vc2_launch_packed(c->L, p, pack, v.n, c->stream);
+}
+
 // The decoder's store for n pictures of g: the slice records, behind them the band planes of the finest levels and the
 // record heads of the deep ones (planned by dry runs of run_inverse: nothing is launched).  decode_batch_common plans the
 // store the slice decoders fill, encode_recon_batch_dev the one the requantise kernel fills for the same inverse kernels.
@@ -1862,7 +2015,7 @@ extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, 
 }
 
 static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f, const int32_t *qm,
-                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const void *d_raw, const ReconOut &ro,
+                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const struct RawView &in, const ReconOut &ro,
                      const int32_t *d_cb, bool check, const LdEncParams *ld);
 
 extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
@@ -1951,7 +2104,14 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
   LLPlanes ll;
   ll_layout(g, n, d_ll, s16 ? 2 : 4, d_llw, ll);
   const void *src[3]; RawPlane ss[3];
-  raw_planes(f, active_layout(c), d_raw, fields, top_first, src, ss);
+  RawView in; // (frames, for fields: n / fields pictures of the buffer)
+  {
+    vc2hip_picture_format fb = *f;
+    fb.height = f->height * fields;
+    if ((rc = raw_view(c, &fb, n / fields, d_raw, B_PKIN, in))) return rc;
+  }
+  view_convert(c, in, false);
+  view_planes(in, f, fields, top_first, src, ss);
   if (needs_plane_path(c, g, cp->kernel)) { // (a slice beyond any LDS tile: HQ and LD alike -- the store is int32 then)
     if ((rc = plane_forward(c, g, cp->kernel, n, src, ss, f, d_store))) return rc;
   } else if ((rc = run_forward(c, g, cp->kernel, n, src, ss, true, f, d_store, ll, s16, d_storew))) return rc;
@@ -1978,7 +2138,7 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
       vc2_launch_ld_pack(c->L, p, n, c->stream);
       vc2_launch_fill_u64(c->L, (unsigned long long *)d_lens, total, (size_t)n, c->stream);
     }
-    return ro ? run_recon(c, g, cp, n, f, qm, false, d_store, nullptr, d_q, ll, d_raw, *ro, d_cb, !d_payload, &p) : VC2HIP_OK;
+    return ro ? run_recon(c, g, cp, n, f, qm, false, d_store, nullptr, d_q, ll, in, *ro, d_cb, !d_payload, &p) : VC2HIP_OK;
   }
   if (cp->mode == VC2HIP_HQ_CBR) {
       const int key[5] = {g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix};
@@ -2025,7 +2185,7 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
   }
   if (d_payload && (rc = run_pack(c, g, n, d_store, d_q, qm, true, cp->prefix, cp->scalar, d_cb, d_co, total, (uint8_t *)d_payload,
                                   (long long)payload_stride, (unsigned long long *)d_lens, s16, d_storew))) return rc;
-  return ro ? run_recon(c, g, cp, n, f, qm, s16, d_store, d_storew, d_q, ll, d_raw, *ro, d_cb, !d_payload, nullptr) : VC2HIP_OK;
+  return ro ? run_recon(c, g, cp, n, f, qm, s16, d_store, d_storew, d_q, ll, in, *ro, d_cb, !d_payload, nullptr) : VC2HIP_OK;
 }
 
 // What follows the slice coder in vc2hip_encode_recon_batch_dev: the indices, the decoder's picture from the quantised
@@ -2033,13 +2193,15 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
 // which k_requantise turns into the decoder's store; LD: vc2_launch_ld_quantise left quantised values with LL residuals in
 // it, which is what the decoder's slice reader leaves.  check: no payload was written, the coder's checks are made here.
 static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f, const int32_t *qm,
-                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const void *d_raw, const ReconOut &ro,
+                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const RawView &in, const ReconOut &ro,
                      const int32_t *d_cb, bool check, const LdEncParams *ld) {
   const int ns = g.ys * g.xs;
   int rc;
   if (ro.qidx) HIPCHK(c, hipMemcpyAsync(ro.qidx, d_q, (size_t)n * ns * 4, hipMemcpyDeviceToDevice, c->stream));
   const void *dstc[3]; RawPlane ds[3];
-  raw_planes(f, active_layout(c), ro.recon, 1, 1, dstc, ds);
+  RawView out;
+  if ((rc = raw_view(c, f, n, ro.recon, B_PKOUT, out))) return rc;
+  view_planes(out, f, 1, 1, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
   if (ld) {
@@ -2089,12 +2251,44 @@ static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *c
       if (rc) return rc;
     }
   }
-  if (ro.sse) {
+  if (ro.recon) view_convert(c, out, true);
+  if (ro.sse && out.packed) { // the two stagings (semi-planar: the Y planes where they are, in a launch of their own)
+    HIPCHK(c, hipMemsetAsync(ro.sse, 0, (size_t)n * 3 * 8, c->stream));
+    vc2_prof_break(c->L);
+    const bool v210 = out.pl.packing == VC2HIP_PACKING_V210;
+    SseParams p;
+    memset(&p, 0, sizeof p);
+    p.word_bytes = f->word_bytes; p.shift = v210 || out.pl.lsb ? 0 : 8 * f->word_bytes - f->bit_depth;
+    p.mask = f->bit_depth < 32 ? (1u << f->bit_depth) - 1 : ~0u;
+    p.le = v210 ? 1 : out.pl.le;
+    p.sse = (unsigned long long *)ro.sse;
+    SseParams ps = p; // the staged components
+    ps.a = in.stage; ps.b = out.stage; ps.pic_bytes = (long long)out.sstride;
+    for (int k = v210 ? 0 : 1; k < 3; ++k) {
+      const long long row = (long long)g.c[k].w * f->word_bytes;
+      const bool tight = (long long)out.spitch[k] == row;
+      ps.comp_at[k] = (long long)out.sat[k];
+      ps.rows[k] = tight ? 1 : g.c[k].h;
+      ps.row_bytes[k] = tight ? row * g.c[k].h : row;
+      ps.pitch[k] = (long long)out.spitch[k];
+    }
+    vc2_launch_squared_error(c->L, ps, n, c->stream);
+    if (!v210) {
+      p.a = (const uint8_t *)in.base; p.b = (const uint8_t *)out.base; p.pic_bytes = (long long)out.pl.stride;
+      const long long row = (long long)g.c[0].w * f->word_bytes;
+      const bool tight = (long long)out.pl.pitch[0] == row;
+      p.comp_at[0] = (long long)out.pl.at[0];
+      p.rows[0] = tight ? 1 : g.c[0].h;
+      p.row_bytes[0] = tight ? row * g.c[0].h : row;
+      p.pitch[0] = (long long)out.pl.pitch[0];
+      vc2_launch_squared_error(c->L, p, n, c->stream);
+    }
+  } else if (ro.sse) {
     HIPCHK(c, hipMemsetAsync(ro.sse, 0, (size_t)n * 3 * 8, c->stream));
     vc2_prof_break(c->L);
     SseParams p;
     memset(&p, 0, sizeof p);
-    p.a = (const uint8_t *)d_raw; p.b = (const uint8_t *)ro.recon;
+    p.a = (const uint8_t *)in.base; p.b = (const uint8_t *)ro.recon;
     RawLayout lay;
     (void)resolve_layout(f, active_layout(c), lay); // (refused at the entry point)
     p.pic_bytes = (long long)lay.stride;
@@ -2159,7 +2353,13 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   }
   const bool s16 = !ld && use_store16(c, g, cp->kernel);
   const void *dstc[3]; RawPlane ds[3];
-  raw_planes(f, active_layout(c), d_raw_out, fields, top_first, dstc, ds);
+  RawView out; // (frames, for fields; the reduced pictures)
+  {
+    vc2hip_picture_format fb = *f;
+    fb.height = f->height * fields;
+    if ((rc = raw_view(c, &fb, n / fields, d_raw_out, B_PKOUT, out))) return rc;
+  }
+  view_planes(out, f, fields, top_first, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
   DecoderLayout lay;
@@ -2313,9 +2513,11 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
                        g.c[k].ph >> g.depth, g.c[k].pw >> g.depth, g.ys, g.xs, d_q, qm[0], (int32_t *)ll.p[g.depth][k],
                        ll.stride[g.depth][k], n, c->d_err, c->stream);
   }
-  if (plane_path) return plane_inverse(c, g, cp->kernel, n, d_store, d_q, qm, dst, ds, f, ld ? &ll : nullptr, norm_shift, drop);
-  return run_inverse(c, g, cp->kernel, n, d_store, d_q, qm, true, ld, ll, dst, ds, true, f, s16, d_storew, &bp, sstride, nullptr,
-                     hs.n[0] ? &hs : nullptr, head_level, nullptr, nullptr, norm_shift, drop);
+  if (plane_path) rc = plane_inverse(c, g, cp->kernel, n, d_store, d_q, qm, dst, ds, f, ld ? &ll : nullptr, norm_shift, drop);
+  else rc = run_inverse(c, g, cp->kernel, n, d_store, d_q, qm, true, ld, ll, dst, ds, true, f, s16, d_storew, &bp, sstride, nullptr,
+                        hs.n[0] ? &hs : nullptr, head_level, nullptr, nullptr, norm_shift, drop);
+  if (!rc) view_convert(c, out, true);
+  return rc;
 }
 
 extern "C" int vc2hip_band_plane_bits(const vc2hip_ctx *c) { return c ? c->last_plane_bits : 0; }

@@ -517,6 +517,23 @@ struct SseParams {
 };
 void vc2_launch_squared_error(Launcher &L, const SseParams &p, int n_pictures, hipStream_t s);
 
+// packed and semi-planar pictures <-> planar staging (vc2hip_packed.hip, vc2hip_set_packed_format)
+struct PackedParams {
+  uint8_t *packed;            // the caller's buffer: picture 0's first v210 row / first row of its UV plane
+  long long packed_stride;    // bytes per picture
+  int packed_pitch;           // bytes from one of those rows to the next
+  uint8_t *plane[3];          // staging planes of picture 0 (the UV kernels use [1] and [2]); rows start on 16-byte boundaries
+  long long plane_stride;     // bytes per picture
+  int plane_pitch[3];
+  int rows;                   // rows of the caller's plane
+  int width;                  // v210: luma samples of a row; UV: word pairs of a row (the chroma width)
+  int v210;                   // 1: the v210 kernels, 0: the UV kernels at word_bytes 1 or 2
+  int word_bytes;
+  int vec;                    // UV: every row of the caller's plane starts on a 16-byte boundary (16-byte pieces)
+};
+// pack: staging -> the caller's buffer; else the caller's buffer -> staging
+void vc2_launch_packed(Launcher &L, const PackedParams &p, bool pack, int n_pictures, hipStream_t s);
+
 // VC-2 stream I/O (vc2hip_stream.hip)
 #define VC2_STREAM_HDR_MAX 48 // picture header bytes the write kernels carry (vc2hip_picture_header is far below it)
 struct StreamWriteParams {

@@ -58,6 +58,13 @@ class SampleLayout(C.Structure):
                 ("plane_offset", C.c_size_t * 3), ("picture_stride", C.c_size_t)]
 
 
+class PackedFormat(C.Structure):
+    """vc2hip_packed_format: v210 or semi-planar pictures on the device batch calls (include/vc2hip.h)"""
+    _fields_ = [("packing", C.c_int), ("little_endian", C.c_int), ("lsb_justified", C.c_int), ("pitch", C.c_size_t * 2),
+                ("plane_offset", C.c_size_t * 2), ("picture_stride", C.c_size_t)]
+
+
+PACKING = {"none": 0, "v210": 1, "semiplanar": 2}   # VC2HIP_PACKING_*
 DWT_FAMILIES = ("tile", "fast", "stream", "pair", "plane")   # VC2HIP_DWT_TILE ... VC2HIP_DWT_PLANE
 
 
@@ -84,6 +91,7 @@ EXPORTS = [
     "vc2hip_encode_fields_batch_dev", "vc2hip_decode_fields_batch_dev", "vc2hip_decode_reduced_batch_dev",
     "vc2hip_encode_recon_batch_dev", "vc2hip_stream_write_fragments_dev",
     "vc2hip_set_sample_layout", "vc2hip_layout_picture_bytes",
+    "vc2hip_set_packed_format", "vc2hip_packed_picture_bytes",
 ]
 
 
@@ -152,6 +160,9 @@ def load_library():
     lib.vc2hip_set_sample_layout.argtypes = [vp, C.POINTER(SampleLayout)]
     lib.vc2hip_layout_picture_bytes.argtypes = [C.POINTER(PictureFormat), C.POINTER(SampleLayout)]
     lib.vc2hip_layout_picture_bytes.restype = C.c_size_t
+    lib.vc2hip_set_packed_format.argtypes = [vp, C.POINTER(PackedFormat)]
+    lib.vc2hip_packed_picture_bytes.argtypes = [C.POINTER(PictureFormat), C.POINTER(PackedFormat)]
+    lib.vc2hip_packed_picture_bytes.restype = C.c_size_t
     lib.vc2hip_picture_header.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, u8p, C.c_size_t,
                                           C.POINTER(C.c_size_t)]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
@@ -200,6 +211,23 @@ def sample_layout(little_endian=False, lsb_justified=False, pitch=(0, 0, 0), pla
 def layout_picture_bytes(lib, fmt, layout=None):
     """vc2hip_layout_picture_bytes (host only): bytes from a picture's base to the end of its furthest plane row; 0: refused"""
     return lib.vc2hip_layout_picture_bytes(C.byref(fmt), C.byref(layout) if layout is not None else None)
+
+
+def packed_format(packing, little_endian=False, lsb_justified=False, pitch=(0, 0), plane_offset=(0, 0), picture_stride=0):
+    """a vc2hip_packed_format; packing: "v210", "semiplanar" or a VC2HIP_PACKING_* number (what the library refuses is passed on).
+    P010 / P210 / P016: packed_format("semiplanar", little_endian=True)."""
+    return PackedFormat(PACKING.get(packing, packing), int(little_endian), int(lsb_justified), (C.c_size_t * 2)(*pitch),
+                        (C.c_size_t * 2)(*plane_offset), picture_stride)
+
+
+def v210_pitch(width, align=128):
+    """bytes of a v210 row of `width` pixels, rounded up to `align` (128: the convention of capture cards; 16: tight)"""
+    return ((width + 5) // 6 * 16 + align - 1) // align * align
+
+
+def packed_picture_bytes(lib, fmt, pf):
+    """vc2hip_packed_picture_bytes (host only): bytes from a picture's base to the end of its furthest row; 0: refused"""
+    return lib.vc2hip_packed_picture_bytes(C.byref(fmt), C.byref(pf) if pf is not None else None)
 
 
 def torch_planes(y, u, v):
@@ -566,6 +594,14 @@ class Vc2Hip:
 
     def layout_picture_bytes(self, fmt, layout=None):
         return layout_picture_bytes(self.lib, fmt, layout)
+
+    def set_packed_format(self, pf=None):
+        """v210 / semi-planar pictures in every raw-sample buffer of the device batch calls from now on (None: off, the
+        sample layout applies again)"""
+        self._chk(self.lib.vc2hip_set_packed_format(self.h, C.byref(pf) if pf is not None else None))
+
+    def packed_picture_bytes(self, fmt, pf):
+        return packed_picture_bytes(self.lib, fmt, pf)
 
     def set_streams(self, k):
         self._chk(self.lib.vc2hip_set_streams(self.h, k))

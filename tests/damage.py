@@ -17,6 +17,7 @@ from collections import namedtuple
 
 import numpy as np
 
+import index_ref
 import proxy_ref as pr
 from synth import noise_frame, synth
 from vc2lib import OracleError
@@ -29,9 +30,8 @@ ESTREAM, EQINDEX = -10, -2                           # VC2O_ESTREAM / VC2O_EQIND
 
 def index_chunk(prefix, scalar):
     """the bytes the slice index takes per chunk: by the longest slice the length bytes can describe (idx_entries and
-    idx_chunk of vc2hip_slices.hip) -- 8 KiB at scalar 1, 16 KiB from scalar 2 on"""
-    entries = prefix + 4 + 3 * 255 * scalar
-    return 8192 if entries <= 1024 else 16384 if entries <= 8191 else 32768
+    idx_chunk of vc2hip_slices.hip, restated in index_ref.plan) -- 8 KiB at scalar 1, 16 KiB from scalar 2 on"""
+    return index_ref.plan(prefix, scalar, 0).CH
 
 
 # the share of a class the oracle must accept, so that "both refuse" cannot carry a comparison (`length`, `hdr0`: no cap)

@@ -202,8 +202,7 @@ struct vc2hip_ctx {
   std::vector<hipEvent_t> join_ev;    // end of lane i's latest sub-batch
   bool lanes_pending = false;         // `stream` has not yet been made to wait for the lanes' latest sub-batches
   struct Range { const uint8_t *lo, *hi; };
-  enum { LANE_RANGES = 5 };            // caller buffers one call reads / writes (encode_recon_batch_dev writes five)
-  struct LaneUse { Range r[LANE_RANGES], w[LANE_RANGES]; bool valid = false; };
+  struct LaneUse { std::vector<Range> r, w; bool valid = false; }; // one range per caller buffer of the call (BatchBuf)
   std::vector<LaneUse> lane_use;      // what lane i's latest sub-batch read and wrote (caller buffers)
   std::vector<ProfEntry> merged; // profile of this context and its lanes, rebuilt by vc2hip_profile_count
   // pipelined picture calls: VC2HIP_MAX_INFLIGHT slots, each a child context (own stream and workspace)
@@ -528,13 +527,21 @@ extern "C" int vc2hip_set_streams(vc2hip_ctx *c, int k) {
   return VC2HIP_OK;
 }
 
-// Run fn(lane, first picture, picture count) for contiguous sub-batches on the lanes' streams.  use(first, count,
-// LaneUse&) names the caller buffers a sub-batch reads and writes.  A lane waits for the context's stream (fork)
-// and for every other lane whose previous sub-batch touched what it is about to touch; consecutive calls with the
-// same partition (encode -> decode of the same batch) therefore chain lane by lane without a barrier.  The
-// context's stream joins the lanes lazily: at the next entry point that uses it, or at once when the stream
-// belongs to the caller (vc2hip_create_on_stream).
-template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, F fn) {
+// One caller buffer of a device batch call.  An item is a picture, or a frame for the two field calls: a frame takes two
+// payload slots and two lengths, and that factor of two is in `each` and nowhere else.
+struct BatchBuf {
+  const void *p; // null where the call allows it: it has no range then, and a lane's pointer stays null
+  size_t each;   // bytes per item
+  bool written;
+};
+
+// Run fn(lane, item count, the buffers' pointers at the lane's first item) for contiguous sub-batches of the n items on the
+// lanes' streams: lane i takes n / k + (i < n % k) of them.  A lane waits for the context's stream (fork) and for every
+// other lane whose previous sub-batch touched what it is about to touch (the buffers' ranges: read against written, written
+// against both); consecutive calls with the same partition (encode -> decode of the same batch) therefore chain lane by
+// lane without a barrier.  The context's stream joins the lanes lazily: at the next entry point that uses it, or at once
+// when the stream belongs to the caller (vc2hip_create_on_stream).
+template <size_t NB, class F> static int split_batch(vc2hip_ctx *c, int n, const BatchBuf (&bufs)[NB], F fn) {
   const int k = std::min<int>((int)c->lanes.size(), n);
   HIPCHK(c, hipSetDevice(c->device));
   // A caller's stream was joined to every lane when the call before returned, and the fork event below follows that join:
@@ -544,12 +551,22 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
   HIPCHK(c, hipEventRecord(c->fork_ev, c->stream));
   std::vector<vc2hip_ctx::LaneUse> cur((size_t)c->lanes.size());
   std::vector<int> first((size_t)k), count((size_t)k);
-  auto overlap = [](const vc2hip_ctx::Range &a, const vc2hip_ctx::Range &b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; };
+  typedef std::vector<vc2hip_ctx::Range> Ranges;
+  auto overlap = [](const Ranges &a, const Ranges &b) {
+    for (const vc2hip_ctx::Range &x : a)
+      for (const vc2hip_ctx::Range &y : b)
+        if (x.lo < y.hi && y.lo < x.hi) return true;
+    return false;
+  };
   for (int i = 0, f0 = 0; i < k; ++i) {
     count[i] = n / k + (i < n % k ? 1 : 0);
     first[i] = f0;
     f0 += count[i];
-    use(first[i], count[i], cur[i]);
+    for (const BatchBuf &b : bufs) {
+      if (!b.p) continue;
+      const uint8_t *lo = (const uint8_t *)b.p + (size_t)first[i] * b.each;
+      (b.written ? cur[i].w : cur[i].r).push_back({lo, lo + (size_t)count[i] * b.each});
+    }
     cur[i].valid = true;
   }
   for (int i = 0; i < k; ++i) { // all waits before any join event is recorded again
@@ -558,11 +575,8 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
     for (size_t j = 0; j < c->lanes.size(); ++j) {
       const vc2hip_ctx::LaneUse &p = c->lane_use[j];
       if ((int)j == i || !p.valid) continue;
-      bool dep = false;
-      for (int a = 0; a < vc2hip_ctx::LANE_RANGES; ++a)
-        for (int b = 0; b < vc2hip_ctx::LANE_RANGES; ++b)
-          dep |= overlap(cur[i].r[a], p.w[b]) || overlap(cur[i].w[a], p.w[b]) || overlap(cur[i].w[a], p.r[b]);
-      if (dep) HIPCHK(c, hipStreamWaitEvent(l->stream, c->join_ev[j], 0));
+      if (overlap(cur[i].r, p.w) || overlap(cur[i].w, p.w) || overlap(cur[i].w, p.r))
+        HIPCHK(c, hipStreamWaitEvent(l->stream, c->join_ev[j], 0));
     }
   }
   int rc = VC2HIP_OK;
@@ -571,7 +585,9 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
     c->in_split = (i == 0);
     l->layout = c->layout; l->has_layout = c->has_layout; // (host state: a lane's pictures lie as the context's)
     l->packed = c->packed; l->has_packed = c->has_packed;
-    const int r = fn(l, first[i], count[i]);
+    void *at[NB];
+    for (size_t b = 0; b < NB; ++b) at[b] = bufs[b].p ? (uint8_t *)bufs[b].p + (size_t)first[i] * bufs[b].each : nullptr;
+    const int r = fn(l, count[i], at);
     c->in_split = false;
     if (r && !rc) rc = i ? set_err(c, r, l->err.c_str()) : r;
     HIPCHK(c, hipEventRecord(c->join_ev[i], l->stream));
@@ -580,6 +596,13 @@ template <class U, class F> static int split_batch(vc2hip_ctx *c, int n, U use, 
   c->lanes_pending = true;
   if (!c->own_stream) return join_lanes(c) ? VC2HIP_EHIP : rc;
   return rc;
+}
+// A device batch call's work, once its front checks have passed: all n items on the context, or cut over its lanes
+template <size_t NB, class F> static int run_batch(vc2hip_ctx *c, int n, const BatchBuf (&bufs)[NB], F fn) {
+  if (c->lanes.size() > 1 && n > 1) return split_batch(c, n, bufs, fn);
+  void *at[NB];
+  for (size_t b = 0; b < NB; ++b) at[b] = (void *)bufs[b].p;
+  return fn(c, n, at);
 }
 
 extern "C" int vc2hip_sync(vc2hip_ctx *c) {
@@ -857,9 +880,8 @@ static int batch_layout(vc2hip_ctx *c, const vc2hip_picture_format *f, RawLayout
   if (const vc2hip_packed_format *pf = active_packed(c)) {
     PackedLayout pl;
     if (const char *e = resolve_packed(f, pf, pl)) return set_err(c, VC2HIP_EINVAL, e);
-    // (lanes cut the batch at the picture stride and every lane's base keeps the 16-byte rule: refused here, before lane 0
-    // is enqueued, not by lane 1's own entry check)
-    if (c->lanes.size() > 1 && !c->in_split && (pl.stride & 15))
+    // (lanes cut the batch at the picture stride and every lane's base keeps the 16-byte rule)
+    if ((pl.stride & 15) && c->lanes.size() > 1)
       return set_err(c, VC2HIP_EINVAL, "packed format: with vc2hip_set_streams(k > 1) the picture stride must be a multiple of 16 bytes");
     memset(&r, 0, sizeof r);
     r.le = pl.le; r.lsb = pl.lsb; r.extent = pl.extent; r.stride = pl.stride;
@@ -1809,16 +1831,14 @@ extern "C" int vc2hip_ld_pack(vc2hip_ctx *c, const int32_t *y, const int32_t *u,
 // ------------------------------------------------------------------------------------------
 // fused picture path
 // ------------------------------------------------------------------------------------------
-// The raw words of a batch of pictures of format f (vc2_raw_pic_offset).  fields == 1: progressive pictures, packed.
-// fields == 2: f is a FIELD's format, the pictures are the fields of packed interleaved frames (2 * f->height rows, and twice
-// the chroma rows), in stream order: the first field of a frame is its even rows when top_first, else its odd rows.
-// lay: the caller's sample layout (null: the file format).  It describes the FRAME's buffer; the field addressing goes on top.
-static void raw_planes(const vc2hip_picture_format *f, const vc2hip_sample_layout *lay, const void *base, int fields, int top_first,
+// The raw words of a batch of pictures (vc2_raw_pic_offset).  fb: the format of the buffer's pictures; lay: the caller's sample
+// layout of them (null: the file format).  fields == 1: the coded pictures are the buffer's.  fields == 2: they are the fields
+// of the buffer's interleaved frames, in stream order: the first field of a frame is its even rows when top_first, else its
+// odd rows -- the field addressing goes on top of the frame's layout.
+static void raw_planes(const vc2hip_picture_format *fb, const vc2hip_sample_layout *lay, const void *base, int fields, int top_first,
                        const void *pl[3], RawPlane rl[3]) {
-  vc2hip_picture_format ff = *f; // the pictures of the buffer
-  ff.height = f->height * fields;
   RawLayout r;
-  (void)resolve_layout(&ff, lay, r); // (refused by the entry points: batch_layout)
+  (void)resolve_layout(fb, lay, r); // (refused by the entry points: batch_layout)
   for (int k = 0; k < 3; ++k) {
     const bool second_first = fields == 2 && !top_first; // (the first field starts on the frame's row 1)
     pl[k] = (const uint8_t *)base + r.at[k] + (second_first ? r.pitch[k] : 0);
@@ -1862,9 +1882,9 @@ static int raw_view(vc2hip_ctx *c, const vc2hip_picture_format *fb, int nbuf, co
   if (base) NEED(c, which, (size_t)nbuf * v.sstride + 16, v.stage);
   return VC2HIP_OK;
 }
-// raw_planes for a view; f: the PICTURES' format (a field's, for fields == 2)
-static void view_planes(const RawView &v, const vc2hip_picture_format *f, int fields, int top_first, const void *pl[3], RawPlane rl[3]) {
-  if (!v.packed) { raw_planes(f, v.lay, v.base, fields, top_first, pl, rl); return; }
+// raw_planes for a view of pictures of format fb
+static void view_planes(const RawView &v, const vc2hip_picture_format *fb, int fields, int top_first, const void *pl[3], RawPlane rl[3]) {
+  if (!v.packed) { raw_planes(fb, v.lay, v.base, fields, top_first, pl, rl); return; }
   const bool v210 = v.pl.packing == VC2HIP_PACKING_V210;
   for (int k = 0; k < 3; ++k) {
     const bool in_place = !v210 && k == 0; // (the Y plane of a semi-planar picture: plane 0 of a layout in the caller's word form)
@@ -1985,58 +2005,76 @@ struct ReconOut {
   uint64_t *sse;   // n x 3 sums of squared differences against d_raw, or null
   int32_t *qidx;   // n x slices, or null
 };
-static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int top_first, int n, const vc2hip_picture_format *f,
-                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
-                               const ReconOut *ro = nullptr);
-
-extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
-                                       const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride,
-                                       uint64_t *d_lens) {
-  if (!c || !d_raw || n < 1 || !f || !cp || !d_payload || !d_lens) return set_err(c, VC2HIP_EINVAL);
-  if (((size_t)d_raw | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
-    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
-  RawLayout lay;
-  if (int rc = batch_layout(c, f, lay)) return rc;
-  if (c->lanes.size() > 1 && n > 1 && !c->in_split) {
-    const size_t rb = lay.stride; // (the file format: vc2hip_raw_picture_bytes)
-    const uint8_t *raw8 = (const uint8_t *)d_raw, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
-    return split_batch(c, n,
-      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
-        u.r[0] = {raw8 + (size_t)first * rb, raw8 + (size_t)(first + count) * rb}; u.r[1] = {nullptr, nullptr};
-        u.w[0] = {pay8 + (size_t)first * payload_stride, pay8 + (size_t)(first + count) * payload_stride};
-        u.w[1] = {len8 + (size_t)first * 8, len8 + (size_t)(first + count) * 8};
-      },
-      [&](vc2hip_ctx *l, int first, int count) {
-        return vc2hip_encode_batch_dev(l, raw8 + (size_t)first * rb, count, f, cp,
-                                       (uint8_t *)d_payload + (size_t)first * payload_stride, payload_stride, d_lens + first);
-      });
-  }
-  return encode_batch_common(c, d_raw, 1, 1, n, f, cp, d_payload, payload_stride, d_lens);
-}
-
+static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, int fields, int top_first, int n,
+                               const vc2hip_picture_format *fb, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
+                               void *d_payload, size_t payload_stride, uint64_t *d_lens, const ReconOut *ro = nullptr);
 static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f, const int32_t *qm,
                      bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const struct RawView &in, const ReconOut &ro,
                      const int32_t *d_cb, bool check, const LdEncParams *ld);
 
+// ---- the front of the six device batch calls -------------------------------------------------------------------------
+// Every call refuses what it can see in its arguments here, before it records the fork event or enters the context: a
+// refused batch call touches no stream, with one lane or several.  An entry point states its arguments once (batch_args),
+// adds the refusals of its own, resolves the caller's layout for the pictures of its buffer (batch_layout), lists its
+// buffers (BatchBuf) and hands the work to run_batch, whose callback calls encode_batch_common / decode_batch_common on
+// the context or on a lane.  Those two check no argument again.
+struct BatchArg {
+  const void *p;
+  unsigned align; // 16 (pictures, payload), 8 (lengths, squared errors) or 4 (indices) bytes
+  bool optional;  // may be null
+};
+static int batch_args(vc2hip_ctx *c, int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, size_t payload_stride,
+                      std::initializer_list<BatchArg> args, const char *null_text = nullptr) {
+  bool missing = !c || n < 1 || !f || !cp, misaligned = (payload_stride & 15) != 0;
+  for (const BatchArg &a : args) {
+    missing = missing || (!a.p && !a.optional);
+    misaligned = misaligned || ((size_t)a.p & (a.align - 1));
+  }
+  if (missing) return set_err(c, VC2HIP_EINVAL, null_text);
+  if (misaligned) return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
+  return VC2HIP_OK;
+}
+// what the three encoding calls refuse in cp; g: the coded picture's geometry
+static int encode_check(vc2hip_ctx *c, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, Geom &g) {
+  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD && cp->mode != VC2HIP_HQ_CAPPED) return set_err(c, VC2HIP_EINVAL);
+  if (cp->mode == VC2HIP_HQ_CAPPED && (cp->q_index < 0 || cp->q_index > VC2_CAP_Q_TOP || cp->compressed_bytes < 1))
+    return set_err(c, VC2HIP_EINVAL, "HQ_CAPPED: q_index 0 .. 115, compressed_bytes >= 1");
+  if (cp->mode != VC2HIP_LD && (cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
+  const int rc = picture_geom(g, f, cp, false);
+  return rc ? set_err(c, rc) : VC2HIP_OK;
+}
+
+extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
+                                       const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride,
+                                       uint64_t *d_lens) {
+  if (int rc = batch_args(c, n, f, cp, payload_stride, {{d_raw, 16}, {d_payload, 16}, {d_lens, 8}})) return rc;
+  RawLayout lay;
+  if (int rc = batch_layout(c, f, lay)) return rc;
+  Geom g;
+  if (int rc = encode_check(c, f, cp, g)) return rc;
+  const BatchBuf bufs[] = {{d_raw, lay.stride, false}, {d_payload, payload_stride, true}, {d_lens, 8, true}};
+  return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    return encode_batch_common(l, g, at[0], 1, 1, count, f, f, cp, at[1], payload_stride, (uint64_t *)at[2]);
+  });
+}
+
 extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
                                              const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
                                              void *d_recon, uint64_t *d_sse, int32_t *d_qidx) {
-  if (!c || !d_raw || n < 1 || !f || !cp) return set_err(c, VC2HIP_EINVAL);
+  if (int rc = batch_args(c, n, f, cp, payload_stride,
+                          {{d_raw, 16}, {d_payload, 16, true}, {d_lens, 8, true}, {d_recon, 16, true}, {d_sse, 8, true}, {d_qidx, 4, true}})) return rc;
   if (!d_payload && !d_recon && !d_sse && !d_qidx) return set_err(c, VC2HIP_EINVAL, "no output asked for");
   if (d_sse && !d_recon) return set_err(c, VC2HIP_EINVAL, "d_sse needs d_recon");
   if ((d_payload != nullptr) != (payload_stride != 0) || (d_payload != nullptr) != (d_lens != nullptr))
     return set_err(c, VC2HIP_EINVAL, "d_payload, payload_stride and d_lens: all or none");
-  if (((size_t)d_raw | (size_t)d_payload | (size_t)d_recon | payload_stride) & 15 || (((size_t)d_lens | (size_t)d_sse) & 7) || ((size_t)d_qidx & 3))
-    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
-  Geom ge;
-  if (picture_geom(ge, f, cp, false)) return set_err(c, VC2HIP_EINVAL);
   RawLayout lay; // one layout for d_raw and d_recon
   if (int rc = batch_layout(c, f, lay)) return rc;
-  const size_t rb = lay.stride, span = (size_t)(n - 1) * lay.stride + lay.extent; // (the file format: n * vc2hip_raw_picture_bytes)
-  const int ns = ge.ys * ge.xs;
-  const uint8_t *raw8 = (const uint8_t *)d_raw;
-  uint8_t *rec8 = (uint8_t *)d_recon;
+  Geom ge;
+  if (int rc = encode_check(c, f, cp, ge)) return rc;
   if (d_recon) {
+    const size_t span = (size_t)(n - 1) * lay.stride + lay.extent; // (the file format: n * vc2hip_raw_picture_bytes)
+    const uint8_t *raw8 = (const uint8_t *)d_raw, *rec8 = (const uint8_t *)d_recon;
     if (rec8 < raw8 + span && raw8 < rec8 + span)
       return set_err(c, VC2HIP_EINVAL, "d_recon overlaps d_raw (the squared error reads the input after the reconstruction is written)");
     if (f->chroma_bit_depth && f->chroma_bit_depth != f->bit_depth)
@@ -2047,48 +2085,23 @@ extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, i
       if (gd.c[k].ph != ge.c[k].ph || gd.c[k].pw != ge.c[k].pw)
         return set_err(c, VC2HIP_EINVAL, "the decoder's padded chroma planes differ from the encoder's: no decoder shows this picture");
   }
-  if (c->lanes.size() > 1 && n > 1 && !c->in_split) {
-    uint8_t *pay8 = (uint8_t *)d_payload;
-    auto rng = [](const void *p, size_t first, size_t count, size_t each) {
-      const uint8_t *q = (const uint8_t *)p;
-      return q ? vc2hip_ctx::Range{q + first * each, q + (first + count) * each} : vc2hip_ctx::Range{nullptr, nullptr};
-    };
-    return split_batch(c, n,
-      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
-        u.r[0] = rng(d_raw, first, count, rb);
-        u.w[0] = rng(d_payload, first, count, payload_stride); u.w[1] = rng(d_lens, first, count, 8);
-        u.w[2] = rng(d_recon, first, count, rb); u.w[3] = rng(d_sse, first, count, 24); u.w[4] = rng(d_qidx, first, count, (size_t)ns * 4);
-      },
-      [&](vc2hip_ctx *l, int first, int count) {
-        return vc2hip_encode_recon_batch_dev(l, raw8 + (size_t)first * rb, count, f, cp, pay8 ? pay8 + (size_t)first * payload_stride : nullptr,
-                                             payload_stride, d_lens ? d_lens + first : nullptr, rec8 ? rec8 + (size_t)first * rb : nullptr,
-                                             d_sse ? d_sse + 3 * (size_t)first : nullptr, d_qidx ? d_qidx + (size_t)first * ns : nullptr);
-      });
-  }
-  const ReconOut ro = {d_recon, d_sse, d_qidx};
-  return encode_batch_common(c, d_raw, 1, 1, n, f, cp, d_payload, payload_stride, d_lens, &ro);
+  const BatchBuf bufs[] = {{d_raw, lay.stride, false}, {d_payload, payload_stride, true}, {d_lens, 8, true},
+                           {d_recon, lay.stride, true}, {d_sse, 24, true}, {d_qidx, (size_t)ge.ys * ge.xs * 4, true}};
+  return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    const ReconOut ro = {at[3], (uint64_t *)at[4], (int32_t *)at[5]};
+    return encode_batch_common(l, ge, at[0], 1, 1, count, f, f, cp, at[1], payload_stride, (uint64_t *)at[2], &ro);
+  });
 }
 
-// n pictures of format f (raw_planes: progressive pictures, or the fields of interleaved frames) -> payload slots
-// ro (vc2hip_encode_recon_batch_dev): d_payload may be null -- no slice coder runs then -- and run_recon follows the coder
-static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int top_first, int n, const vc2hip_picture_format *f,
-                               const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride, uint64_t *d_lens,
-                               const ReconOut *ro) {
-  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD && cp->mode != VC2HIP_HQ_CAPPED) return set_err(c, VC2HIP_EINVAL);
-  if (cp->mode == VC2HIP_HQ_CAPPED && (cp->q_index < 0 || cp->q_index > VC2_CAP_Q_TOP || cp->compressed_bytes < 1))
-    return set_err(c, VC2HIP_EINVAL, "HQ_CAPPED: q_index 0 .. 115, compressed_bytes >= 1");
-  if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
-  if (cp->mode != VC2HIP_LD && (cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
-  Geom g;
-  int rc = picture_geom(g, f, cp, false);
-  if (rc) return set_err(c, rc);
-  { // the caller's sample layout against the buffer's pictures (frames, for fields): refused before anything is enqueued
-    vc2hip_picture_format fb = *f;
-    fb.height = f->height * fields;
-    RawLayout lay;
-    if ((rc = batch_layout(c, &fb, lay))) return rc;
-  }
+// n coded pictures of geometry g and sample format f -> payload slots.  fb: the format of the pictures in d_raw, which are
+// the coded pictures (fields 1) or the interleaved frames whose fields they are (fields 2, n / 2 frames: raw_planes).
+// ro (vc2hip_encode_recon_batch_dev): d_payload may be null -- no slice coder runs then -- and run_recon follows the coder.
+// The arguments are the entry point's, checked there.
+static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, int fields, int top_first, int n,
+                               const vc2hip_picture_format *fb, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
+                               void *d_payload, size_t payload_stride, uint64_t *d_lens, const ReconOut *ro) {
   ENTER(c);
+  int rc;
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
   if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
@@ -2104,14 +2117,10 @@ static int encode_batch_common(vc2hip_ctx *c, const void *d_raw, int fields, int
   LLPlanes ll;
   ll_layout(g, n, d_ll, s16 ? 2 : 4, d_llw, ll);
   const void *src[3]; RawPlane ss[3];
-  RawView in; // (frames, for fields: n / fields pictures of the buffer)
-  {
-    vc2hip_picture_format fb = *f;
-    fb.height = f->height * fields;
-    if ((rc = raw_view(c, &fb, n / fields, d_raw, B_PKIN, in))) return rc;
-  }
+  RawView in;
+  if ((rc = raw_view(c, fb, n / fields, d_raw, B_PKIN, in))) return rc;
   view_convert(c, in, false);
-  view_planes(in, f, fields, top_first, src, ss);
+  view_planes(in, fb, fields, top_first, src, ss);
   if (needs_plane_path(c, g, cp->kernel)) { // (a slice beyond any LDS tile: HQ and LD alike -- the store is int32 then)
     if ((rc = plane_forward(c, g, cp->kernel, n, src, ss, f, d_store))) return rc;
   } else if ((rc = run_forward(c, g, cp->kernel, n, src, ss, true, f, d_store, ll, s16, d_storew))) return rc;
@@ -2309,57 +2318,31 @@ static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *c
   return VC2HIP_OK;
 }
 
-static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
-                               const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out, bool ld,
-                               int fields = 1, int top_first = 1, int drop = 0) {
-  if (!c || !d_payload || n < 1 || !f || !cp || !d_raw_out) return set_err(c, VC2HIP_EINVAL);
-  if (((size_t)d_raw_out | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
-    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
-  if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
-  Geom g;
-  int rc = picture_geom(g, f, cp, true);
-  if (rc) return set_err(c, rc);
-  { // the caller's sample layout against the pictures of d_raw_out (frames, for fields; the reduced pictures): as the encoder
-    vc2hip_picture_format fb = *f;
-    fb.height = (f->height * fields) >> drop; fb.width = f->width >> drop;
-    RawLayout lay;
-    if ((rc = batch_layout(c, &fb, lay))) return rc;
-  }
+// n coded pictures in payload slots -> the pictures of d_raw_out, whose format is fb: the coded pictures (fields 1), the
+// interleaved frames whose fields they are (fields 2, n / 2 frames), or -- drop > 0 -- the pictures at 1 / 2^drop size.
+// g: the geometry the level kernels run on; f: the sample format.  The arguments are the entry point's, checked there.
+//
+// A reduced picture (vc2hip_decode_reduced_batch_dev): without its `drop` finest levels the coded
+// picture IS a picture of depth - drop levels whose planes and slices are 2^drop times smaller each way, on the same
+// slice grid, with the first 3 (depth - drop) + 1 entries of the quantisation matrix (it is ordered coarse to fine).
+// g is that picture's: store layout, band planes, record heads and level kernels are planned for it as for any other.
+// What is left of the coded one: where a slice's bytes are (the index kernels walk length bytes, and the slice decoders
+// find a component by them, read its first sh * sw coefficients and leave), and the low-pass gain of the dropped levels,
+// which the launch that writes the raw words takes out (LevelParams::norm_shift).
+static int decode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
+                               const vc2hip_picture_format *fb, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
+                               void *d_raw_out, bool ld, int fields = 1, int top_first = 1, int drop = 0) {
   ENTER(c);
+  int rc;
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
   if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
-  // A reduced picture (vc2hip_decode_reduced_batch_dev): without its `drop` finest levels the coded
-  // picture IS a picture of depth - drop levels whose planes and slices are 2^drop times smaller each way, on the same
-  // slice grid, with the first 3 (depth - drop) + 1 entries of the quantisation matrix (it is ordered coarse to fine).
-  // From here on g and f are that picture's: store layout, band planes, record heads and level kernels are planned for
-  // it as for any other.  What is left of the coded one: where a slice's bytes are (the index kernels walk length bytes,
-  // and the slice decoders find a component by them, read its first sh * sw coefficients and leave), and the low-pass
-  // gain of the dropped levels, which the launch that writes the raw words takes out (LevelParams::norm_shift).
-  vc2hip_picture_format fr;
-  int norm_shift = 0;
-  if (drop) { // (what the call refuses it has refused already: reduced_check)
-    if (fields != 1) return set_err(c, VC2HIP_EINVAL);
-    int h[3], w[3], ph[3], pw[3];
-    for (int k = 0; k < 3; ++k) {
-      const CompGeom &cg = g.c[k];
-      h[k] = cg.h >> drop; w[k] = cg.w >> drop; ph[k] = cg.ph >> drop; pw[k] = cg.pw >> drop;
-    }
-    if ((rc = make_geom(g, ph, pw, h, w, cp->depth - drop, cp->y_slices, cp->x_slices))) return set_err(c, rc);
-    fr = *f;
-    fr.width = f->width >> drop; fr.height = f->height >> drop;
-    f = &fr;
-    norm_shift = drop * (cp->kernel == VC2HIP_HAAR0 ? 0 : cp->kernel == VC2HIP_FIDELITY ? 2 : 1);
-  }
+  const int norm_shift = drop * (cp->kernel == VC2HIP_HAAR0 ? 0 : cp->kernel == VC2HIP_FIDELITY ? 2 : 1);
   const bool s16 = !ld && use_store16(c, g, cp->kernel);
   const void *dstc[3]; RawPlane ds[3];
-  RawView out; // (frames, for fields; the reduced pictures)
-  {
-    vc2hip_picture_format fb = *f;
-    fb.height = f->height * fields;
-    if ((rc = raw_view(c, &fb, n / fields, d_raw_out, B_PKOUT, out))) return rc;
-  }
-  view_planes(out, f, fields, top_first, dstc, ds);
+  RawView out;
+  if ((rc = raw_view(c, fb, n / fields, d_raw_out, B_PKOUT, out))) return rc;
+  view_planes(out, fb, fields, top_first, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
   DecoderLayout lay;
@@ -2423,7 +2406,6 @@ static int decode_batch_common(vc2hip_ctx *c, const void *d_payload, size_t payl
   LLPlanes ll;
   ll_layout(g, n, d_ll, s16 ? 2 : 4, d_llw, ll);
   if (!ld) {
-    if (!d_lens || cp->scalar < 1 || cp->prefix < 0) return set_err(c, VC2HIP_EINVAL);
     uint32_t *d_offs;
     const int32_t *d_cb = nullptr; const uint32_t *d_co = nullptr; uint64_t cbr_total = 0;
     if (cp->mode == VC2HIP_HQ_CBR && cp->compressed_bytes > 0 && c->allow_cbr_index) { // the caller says CBR: the budgets predict the offsets
@@ -2698,73 +2680,66 @@ extern "C" int vc2hip_dwt_launches(const vc2hip_ctx *c, vc2hip_dwt_launch *out, 
   return n;
 }
 
-extern "C" int vc2hip_decode_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
-                                       int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out) {
-  if (c && c->lanes.size() > 1 && n > 1 && !c->in_split && d_payload && f && cp && d_raw_out) {
-    RawLayout lay;
-    if (int rc = batch_layout(c, f, lay)) return rc;
-    const size_t rb = lay.stride;
-    const uint8_t *out8 = (const uint8_t *)d_raw_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
-    return split_batch(c, n,
-      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
-        u.r[0] = {pay8 + (size_t)first * payload_stride, pay8 + (size_t)(first + count) * payload_stride};
-        u.r[1] = {len8 ? len8 + (size_t)first * 8 : nullptr, len8 ? len8 + (size_t)(first + count) * 8 : nullptr};
-        u.w[0] = {out8 + (size_t)first * rb, out8 + (size_t)(first + count) * rb}; u.w[1] = {nullptr, nullptr};
-      },
-      [&](vc2hip_ctx *l, int first, int count) {
-        return vc2hip_decode_batch_dev(l, pay8 + (size_t)first * payload_stride, payload_stride,
-                                       d_lens ? d_lens + first : nullptr, count, f, cp, (uint8_t *)d_raw_out + (size_t)first * rb);
-      });
-  }
-  return decode_batch_common(c, d_payload, payload_stride, d_lens, n, f, cp, d_raw_out, cp && cp->mode == VC2HIP_LD);
+// what the three decoding calls refuse in cp; g: the coded picture's geometry
+static int decode_check(vc2hip_ctx *c, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, const uint64_t *d_lens, bool ld, Geom &g) {
+  if (!ld && (!d_lens || cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
+  const int rc = picture_geom(g, f, cp, true);
+  return rc ? set_err(c, rc) : VC2HIP_OK;
 }
 
-// Pictures at 1 / 2^drop_levels size (include/vc2hip.h): fmt and cp are the CODED picture's; the split over lanes is by
+// vc2hip_decode_batch_dev, and the one picture of the host-buffer calls (ld: the call's, whatever cp->mode says)
+static int decode_batch(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
+                        const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out, bool ld) {
+  if (int rc = batch_args(c, n, f, cp, payload_stride, {{d_raw_out, 16}, {d_payload, 16}, {d_lens, 8, true}})) return rc;
+  Geom g;
+  if (int rc = decode_check(c, f, cp, d_lens, ld, g)) return rc;
+  RawLayout lay;
+  if (int rc = batch_layout(c, f, lay)) return rc;
+  const BatchBuf bufs[] = {{d_payload, payload_stride, false}, {d_lens, 8, false}, {d_raw_out, lay.stride, true}};
+  return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    return decode_batch_common(l, g, at[0], payload_stride, (const uint64_t *)at[1], count, f, f, cp, at[2], ld);
+  });
+}
+extern "C" int vc2hip_decode_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
+                                       int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out) {
+  return decode_batch(c, d_payload, payload_stride, d_lens, n, f, cp, d_raw_out, cp && cp->mode == VC2HIP_LD);
+}
+
+// Pictures at 1 / 2^drop_levels size (include/vc2hip.h): f and cp are the CODED picture's; the split over lanes is by
 // pictures, as the full decoder's, with the smaller pictures' size in the output
 extern "C" int vc2hip_decode_reduced_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
                                                int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, int drop_levels,
                                                void *d_raw_out) {
-  if (!c || !d_payload || n < 1 || !f || !cp || !d_raw_out) return set_err(c, VC2HIP_EINVAL);
-  if (((size_t)d_raw_out | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
-    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
-  // refused before anything is enqueued, on any lane
-  if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
+  if (int rc = batch_args(c, n, f, cp, payload_stride, {{d_raw_out, 16}, {d_payload, 16}, {d_lens, 8, true}})) return rc;
   if (drop_levels < 1 || drop_levels >= cp->depth)
     return set_err(c, VC2HIP_EINVAL, "decode_reduced_batch_dev: drop_levels must be 1 ... depth - 1 (one transform level at least is kept)");
   if (cp->kernel == VC2HIP_DAUB97)
     return set_err(c, VC2HIP_EINVAL, "decode_reduced_batch_dev: Daub97's low-pass gain per level (about 3.03) is no power of two, so a shift cannot normalise its reduced pictures");
-  {
-    Geom g;
-    const int rc = picture_geom(g, f, cp, true);
-    if (rc) return set_err(c, rc);
-    for (int k = 0; k < 3; ++k)
-      if ((g.c[k].h | g.c[k].w) & ((1 << drop_levels) - 1))
-        return set_err(c, VC2HIP_EINVAL, "decode_reduced_batch_dev: every component's width and height must be a multiple of 2^drop_levels");
+  const bool ld = cp->mode == VC2HIP_LD;
+  Geom g;
+  if (int rc = decode_check(c, f, cp, d_lens, ld, g)) return rc;
+  int h[3], w[3], ph[3], pw[3];
+  for (int k = 0; k < 3; ++k) {
+    const CompGeom &cg = g.c[k];
+    if ((cg.h | cg.w) & ((1 << drop_levels) - 1))
+      return set_err(c, VC2HIP_EINVAL, "decode_reduced_batch_dev: every component's width and height must be a multiple of 2^drop_levels");
+    h[k] = cg.h >> drop_levels; w[k] = cg.w >> drop_levels; ph[k] = cg.ph >> drop_levels; pw[k] = cg.pw >> drop_levels;
   }
-  if (c->lanes.size() > 1 && n > 1 && !c->in_split) {
-    vc2hip_picture_format fr = *f;
-    fr.width = f->width >> drop_levels; fr.height = f->height >> drop_levels;
-    RawLayout lay; // (of the reduced pictures' buffer)
-    if (int rc2 = batch_layout(c, &fr, lay)) return rc2;
-    const size_t rb = lay.stride;
-    const uint8_t *out8 = (const uint8_t *)d_raw_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
-    return split_batch(c, n,
-      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
-        u.r[0] = {pay8 + (size_t)first * payload_stride, pay8 + (size_t)(first + count) * payload_stride};
-        u.r[1] = {len8 ? len8 + (size_t)first * 8 : nullptr, len8 ? len8 + (size_t)(first + count) * 8 : nullptr};
-        u.w[0] = {out8 + (size_t)first * rb, out8 + (size_t)(first + count) * rb}; u.w[1] = {nullptr, nullptr};
-      },
-      [&](vc2hip_ctx *l, int first, int count) {
-        return vc2hip_decode_reduced_batch_dev(l, pay8 + (size_t)first * payload_stride, payload_stride,
-                                               d_lens ? d_lens + first : nullptr, count, f, cp, drop_levels,
-                                               (uint8_t *)d_raw_out + (size_t)first * rb);
-      });
-  }
-  return decode_batch_common(c, d_payload, payload_stride, d_lens, n, f, cp, d_raw_out, cp->mode == VC2HIP_LD, 1, 1, drop_levels);
+  // the picture the kept levels make (decode_batch_common), and the format of the pictures in d_raw_out
+  if (int rc = make_geom(g, ph, pw, h, w, cp->depth - drop_levels, cp->y_slices, cp->x_slices)) return set_err(c, rc);
+  vc2hip_picture_format fr = *f;
+  fr.width = f->width >> drop_levels; fr.height = f->height >> drop_levels;
+  RawLayout lay;
+  if (int rc = batch_layout(c, &fr, lay)) return rc;
+  const BatchBuf bufs[] = {{d_payload, payload_stride, false}, {d_lens, 8, false}, {d_raw_out, lay.stride, true}};
+  return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    return decode_batch_common(l, g, at[0], payload_stride, (const uint64_t *)at[1], count, &fr, f, cp, at[2], ld, 1, 1, drop_levels);
+  });
 }
 
 // Field pictures of interleaved frames (include/vc2hip.h): a field has the frame's format at half its height, so the
 // frame's luma and chroma heights must be even (as the host tools require of an interlaced frame: host/Frame.cpp).
+// An item of the two calls is a frame: two payload slots and two lengths.
 static int field_format(vc2hip_ctx *c, const vc2hip_picture_format *frame, vc2hip_picture_format *field) {
   int ch, cw;
   chroma_dims(frame->height, frame->width, frame->chroma_format, &ch, &cw);
@@ -2778,60 +2753,37 @@ static int field_format(vc2hip_ctx *c, const vc2hip_picture_format *frame, vc2hi
 extern "C" int vc2hip_encode_fields_batch_dev(vc2hip_ctx *c, const void *d_frames, int n_frames, const vc2hip_picture_format *frame_fmt,
                                               int top_field_first, const vc2hip_coding_params *cp, void *d_payload,
                                               size_t payload_stride, uint64_t *d_lens) {
-  if (!c || !d_frames || n_frames < 1 || !frame_fmt || !cp || !d_payload || !d_lens)
-    return set_err(c, VC2HIP_EINVAL, "encode_fields_batch_dev: a null argument or fewer than one frame");
-  if (((size_t)d_frames | (size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens & 7))
-    return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  if (int rc = batch_args(c, n_frames, frame_fmt, cp, payload_stride, {{d_frames, 16}, {d_payload, 16}, {d_lens, 8}},
+                          "encode_fields_batch_dev: a null argument or fewer than one frame")) return rc;
   vc2hip_picture_format ff;
-  int rc = field_format(c, frame_fmt, &ff);
-  if (rc) return rc;
-  if (c->lanes.size() > 1 && n_frames > 1 && !c->in_split) { // whole frames per lane: frames [first, first + count), slots twice that
-    RawLayout lay; // (the FRAME's)
-    if ((rc = batch_layout(c, frame_fmt, lay))) return rc;
-    const size_t fb = lay.stride;
-    const uint8_t *raw8 = (const uint8_t *)d_frames, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
-    return split_batch(c, n_frames,
-      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
-        u.r[0] = {raw8 + (size_t)first * fb, raw8 + (size_t)(first + count) * fb}; u.r[1] = {nullptr, nullptr};
-        u.w[0] = {pay8 + (size_t)2 * first * payload_stride, pay8 + (size_t)2 * (first + count) * payload_stride};
-        u.w[1] = {len8 + (size_t)2 * first * 8, len8 + (size_t)2 * (first + count) * 8};
-      },
-      [&](vc2hip_ctx *l, int first, int count) {
-        return vc2hip_encode_fields_batch_dev(l, raw8 + (size_t)first * fb, count, frame_fmt, top_field_first, cp,
-                                              (uint8_t *)d_payload + (size_t)2 * first * payload_stride, payload_stride,
-                                              d_lens + 2 * first);
-      });
-  }
-  return encode_batch_common(c, d_frames, 2, top_field_first != 0, 2 * n_frames, &ff, cp, d_payload, payload_stride, d_lens);
+  if (int rc = field_format(c, frame_fmt, &ff)) return rc;
+  RawLayout lay; // (the FRAME's)
+  if (int rc = batch_layout(c, frame_fmt, lay)) return rc;
+  Geom g;
+  if (int rc = encode_check(c, &ff, cp, g)) return rc;
+  const BatchBuf bufs[] = {{d_frames, lay.stride, false}, {d_payload, 2 * payload_stride, true}, {d_lens, 16, true}};
+  return run_batch(c, n_frames, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    return encode_batch_common(l, g, at[0], 2, top_field_first != 0, 2 * count, frame_fmt, &ff, cp, at[1], payload_stride, (uint64_t *)at[2]);
+  });
 }
 
 extern "C" int vc2hip_decode_fields_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
                                               int n_frames, const vc2hip_picture_format *frame_fmt, int top_field_first,
                                               const vc2hip_coding_params *cp, void *d_frames_out) {
-  if (!c || !d_payload || n_frames < 1 || !frame_fmt || !cp || !d_frames_out)
-    return set_err(c, VC2HIP_EINVAL, "decode_fields_batch_dev: a null argument or fewer than one frame");
+  if (int rc = batch_args(c, n_frames, frame_fmt, cp, payload_stride, {{d_frames_out, 16}, {d_payload, 16}, {d_lens, 8, true}},
+                          "decode_fields_batch_dev: a null argument or fewer than one frame")) return rc;
   vc2hip_picture_format ff;
-  int rc = field_format(c, frame_fmt, &ff);
-  if (rc) return rc;
-  if (c->lanes.size() > 1 && n_frames > 1 && !c->in_split) {
-    RawLayout lay;
-    if ((rc = batch_layout(c, frame_fmt, lay))) return rc;
-    const size_t fb = lay.stride;
-    const uint8_t *out8 = (const uint8_t *)d_frames_out, *pay8 = (const uint8_t *)d_payload, *len8 = (const uint8_t *)d_lens;
-    return split_batch(c, n_frames,
-      [&](int first, int count, vc2hip_ctx::LaneUse &u) {
-        u.r[0] = {pay8 + (size_t)2 * first * payload_stride, pay8 + (size_t)2 * (first + count) * payload_stride};
-        u.r[1] = {len8 ? len8 + (size_t)2 * first * 8 : nullptr, len8 ? len8 + (size_t)2 * (first + count) * 8 : nullptr};
-        u.w[0] = {out8 + (size_t)first * fb, out8 + (size_t)(first + count) * fb}; u.w[1] = {nullptr, nullptr};
-      },
-      [&](vc2hip_ctx *l, int first, int count) {
-        return vc2hip_decode_fields_batch_dev(l, pay8 + (size_t)2 * first * payload_stride, payload_stride,
-                                              d_lens ? d_lens + 2 * first : nullptr, count, frame_fmt, top_field_first, cp,
-                                              (uint8_t *)d_frames_out + (size_t)first * fb);
-      });
-  }
-  return decode_batch_common(c, d_payload, payload_stride, d_lens, 2 * n_frames, &ff, cp, d_frames_out, cp->mode == VC2HIP_LD, 2,
-                             top_field_first != 0);
+  if (int rc = field_format(c, frame_fmt, &ff)) return rc;
+  const bool ld = cp->mode == VC2HIP_LD;
+  Geom g;
+  if (int rc = decode_check(c, &ff, cp, d_lens, ld, g)) return rc;
+  RawLayout lay; // (the FRAME's)
+  if (int rc = batch_layout(c, frame_fmt, lay)) return rc;
+  const BatchBuf bufs[] = {{d_payload, 2 * payload_stride, false}, {d_lens, 16, false}, {d_frames_out, lay.stride, true}};
+  return run_batch(c, n_frames, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    return decode_batch_common(l, g, at[0], payload_stride, (const uint64_t *)at[1], 2 * count, frame_fmt, &ff, cp, at[2], ld, 2,
+                               top_field_first != 0);
+  });
 }
 
 extern "C" int vc2hip_encode_picture_hq(vc2hip_ctx *c, const void *raw, const vc2hip_picture_format *f,
@@ -2880,7 +2832,7 @@ static int decode_picture_host(vc2hip_ctx *c, const uint8_t *payload, size_t len
   HIPCHK(c, hipMemcpyAsync(d_pay, payload, len, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_len, &l64, 8, hipMemcpyHostToDevice, c->stream));
   const LayoutBypass file_format(c); // (the host-buffer calls keep the file format)
-  int rc = decode_batch_common(c, d_pay, stride, (const uint64_t *)d_len, 1, f, cp, d_raw, ld);
+  int rc = decode_batch(c, d_pay, stride, (const uint64_t *)d_len, 1, f, cp, d_raw, ld);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(raw_out, d_raw, rb, hipMemcpyDeviceToHost, c->stream));
   return vc2hip_sync(c);
@@ -2976,7 +2928,7 @@ extern "C" int vc2hip_decode_picture_begin(vc2hip_ctx *c, const uint8_t *payload
   *fl->h_len = len;
   if (hipMemcpyAsync(d_pay, payload, len, hipMemcpyHostToDevice, l->stream) != hipSuccess ||
       hipMemcpyAsync(d_len, fl->h_len, 8, hipMemcpyHostToDevice, l->stream) != hipSuccess) return fail(VC2HIP_EHIP);
-  if ((rc = decode_batch_common(l, d_pay, stride, (const uint64_t *)d_len, 1, f, cp, d_raw, cp->mode == VC2HIP_LD))) return fail(rc);
+  if ((rc = decode_batch(l, d_pay, stride, (const uint64_t *)d_len, 1, f, cp, d_raw, cp->mode == VC2HIP_LD))) return fail(rc);
   if (hipMemcpyAsync(raw_out, d_raw, rb, hipMemcpyDeviceToHost, l->stream) != hipSuccess) return fail(VC2HIP_EHIP);
   return VC2HIP_OK;
 }

@@ -496,6 +496,56 @@ int vc2hip_decode_fields_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_
                                    const uint64_t *d_lens, int n_frames, const vc2hip_picture_format *frame_fmt,
                                    int top_field_first, const vc2hip_coding_params *cp, void *d_frames_out);
 
+/* Coded HQ pictures to a coarser quantiser index, slots in and slots out, without leaving the coefficient domain: what a
+ * device-resident stream pipeline needs between vc2hip_stream_read_dev and vc2hip_stream_write_dev to put pictures on a
+ * narrower link or under a byte cap.  No transform runs; the route through vc2hip_decode_batch_dev and
+ * vc2hip_encode_batch_dev costs four transform passes, a clip and a second rounding.
+ * Per picture i, from slot[:min(d_lens_in[i], payload_stride_in)] and an index q_i:
+ *   1. the slices are read as vc2hip_decode_batch_dev reads them: quantised coefficients and every slice's own index q_s;
+ *   2. slice s ends at q'_s = max(q_s, q_i).  A slice with q'_s == q_s keeps its coefficient values: no arithmetic is done on
+ *      them.  Every other coefficient c becomes quant(scale(c, q_s), q'_s) (Quantisation.cpp:69-95) with the default
+ *      quantisation matrix of cp's wavelet and depth, per band max(q - matrix[band], 0) as everywhere;
+ *   3. the result is written as vc2hip_hq_pack writes VBR slices: trailing zeros trimmed, each component rounded up to the
+ *      scalar.  Always a plain HQ VBR payload at cp's prefix and scalar, never finer than the input; HQ_CBR input loses its
+ *      padding.  |c'| <= |c| everywhere and the length never grows with q_i.
+ * q_i = tp->q_index when tp->cap_bytes == 0.  With a cap it is the smallest index in [q_index, 115] at which step 3 does not
+ * refuse and the payload is at most cap_bytes; if there is none, q_i = 115: the picture is coded there without an error of its
+ * own and the caller sees d_lens_out[i] > cap_bytes -- VC2HIP_HQ_CAPPED's rule on coded input, found on the device.
+ * This is not the encode of the original picture at q_i: quantising twice loses a little against quantising once.
+ *   fmt, cp      the CODED pictures', as for vc2hip_decode_batch_dev: VC2HIP_HQ_CONSTQ, HQ_CBR (which may take the budget-claim
+ *                index) and HQ_CAPPED; VC2HIP_LD is refused.  Field pictures are slots like any other: n = 2 * n_frames with
+ *                the field's fmt and cp
+ *   d_qidx       n x y_slices * x_slices int32, raster order, or NULL: q'_s of every output slice
+ * The batch calls' contract above, word for word: slots and strides 16-byte aligned, lengths 8-byte, d_qidx 4-byte;
+ * asynchronous on the ctx stream; nothing allocated, copied to the host or waited for after the first call of a geometry and n;
+ * a caller's stream, graph capture after a warm-up, vc2hip_set_streams lanes as parallel branches, results identical; every
+ * context flag gives the same bytes; a context may mix this call with every other one in any order.
+ * VC2HIP_EINVAL, nothing launched, no output byte touched: a null tp, fmt, cp, input or output pointer or d_lens_out; n < 1;
+ * LD; q_index outside 0 .. VC2HIP_CAP_Q_TOP; cap_bytes < 0; misalignment; output slots that overlap the input slots; a
+ * geometry the decoder refuses.  VC2HIP_ECAP, on the host: payload_stride_out < vc2hip_max_payload_bytes(fmt, cp), or
+ * below y_slices * x_slices * (prefix + 4 + 3 * 255 * scalar) -- vc2hip_max_payload_bytes under HQ_CONSTQ, the bound of the
+ * VBR payload the call writes.  Under an HQ_CBR cp the second is the larger: the budget does not bound what slot bytes no
+ * encoder wrote may ask for, and no output slice is ever cut.
+ * Input no encoder wrote: for every byte string and length the call gives the bytes of steps 1 - 3 or refuses at vc2hip_sync
+ * as they do -- VC2HIP_ESTREAM where the slice reader runs off the end, VC2HIP_EQINDEX for an index above 119,
+ * VC2HIP_ESCALAR / VC2HIP_ECODE32 where the slice writer refuses.  The other pictures of the batch are what they would have
+ * been alone; no byte outside the n output slots, d_lens_out and d_qidx is written; no input byte at or past
+ * min(d_lens_in[i], payload_stride_in) is read; the bytes of an output slot past d_lens_out[i] are unspecified.  Pictures whose
+ * decoded values leave the encoder's domain (|c| > 65534, an index of 116 .. 119) are held to those memory and isolation
+ * rules only.
+ * Not provided: LD, a change of prefix or scalar, a per-slice budget (HQ_CBR output), custom quantisation matrices, an option
+ * of the command-line tools.  Extension, no counterpart in the reference. */
+typedef struct {
+  int q_index;    /* the target: every slice ends at max(its own index, q_i); 0 .. VC2HIP_CAP_Q_TOP */
+  int cap_bytes;  /* 0: no cap, q_i = q_index.  >= 1: per-picture cap on the output payload, q_i found on the device */
+} vc2hip_transcode_params;
+int vc2hip_transcode_batch_dev(vc2hip_ctx *ctx,
+        const void *d_payload_in, size_t payload_stride_in, const uint64_t *d_lens_in, int n,
+        const vc2hip_picture_format *fmt, const vc2hip_coding_params *cp,
+        const vc2hip_transcode_params *tp,
+        void *d_payload_out, size_t payload_stride_out, uint64_t *d_lens_out,
+        int32_t *d_qidx /* n x y_slices * x_slices output indices, raster order, or NULL */);
+
 /* ---------------------------------------------------------------------------------------------
  * VC-2 streams in device memory: the picture data units around the slots of the batch calls
  *

@@ -15,6 +15,7 @@
 #include "vc2hip_internal.h"
 
 void vc2_upload_tables_slices(const QuantTables &t, hipStream_t s);
+void vc2_upload_tables_transcode(const QuantTables &t, hipStream_t s);
 int vc2_halo_x(int kernel);
 int vc2_halo_y(int kernel);
 void vc2_upload_vlc_lut(hipStream_t s);
@@ -134,6 +135,7 @@ enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS,
        B_PLANE_QM,          // plane_inverse: the quantisation matrix of plane_qm_key
        B_CAPTAB,            // HQ_CAPPED: the per-picture length table (vc2hip_cap.h)
        B_PKIN, B_PKOUT,     // vc2hip_set_packed_format: the planar staging of a call's input and of its output pictures
+       B_TCLEN, B_TCQ,      // vc2hip_transcode_batch_dev: the indices handed to the slice coder, the pictures' indices of the capped form
        B_COUNT };
 
 struct vc2hip_ctx {
@@ -414,6 +416,7 @@ static int create_common(int device, hipStream_t stream, bool own, vc2hip_ctx **
   vc2_upload_tables_pair(t, c->stream);
   vc2_upload_tables_stream(t, c->stream);
   vc2_upload_tables_recon(t, c->stream);
+  vc2_upload_tables_transcode(t, c->stream);
   vc2_upload_vlc_lut(c->stream);
   vc2_upload_unpack_lut(c->stream);
   if (hipStreamSynchronize(c->stream) != hipSuccess) { delete c; return VC2HIP_EHIP; }
@@ -2318,6 +2321,26 @@ static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *c
   return VC2HIP_OK;
 }
 
+// HQ_CBR pictures on the decoding side: the caller says CBR, so the budgets predict the slice offsets (the claim that
+// vc2_launch_cbr_index verifies).  The budget tables of cp, uploaded when they are not the ones the context holds; all
+// three stay null / 0 where cp is not HQ_CBR or the context never claims (VC2HIP_FLAG_NO_CBR_INDEX).
+static void cbr_claim_tables(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, const int32_t **d_cb, const uint32_t **d_co,
+                             uint64_t *cbr_total) {
+  if (!(cp->mode == VC2HIP_HQ_CBR && cp->compressed_bytes > 0 && c->allow_cbr_index)) return;
+  const int ns = g.ys * g.xs;
+  const int key[5] = {g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix};
+  if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
+    std::vector<int32_t> sb(ns);
+    int32_t *db; uint32_t *dof; uint64_t total;
+    if (vc2hip_slice_bytes(g.ys, g.xs, cp->compressed_bytes, cp->scalar, sb.data()) == VC2HIP_OK &&
+        cbr_offsets_upload(c, sb.data(), ns, cp->prefix, &db, &dof, &total) == VC2HIP_OK) {
+      memcpy(c->cbr_key, key, sizeof key);
+      c->cbr_total = total;
+    }
+  }
+  if (!memcmp(key, c->cbr_key, sizeof key)) { *d_cb = (const int32_t *)c->buf[B_CBRB].p; *d_co = (const uint32_t *)c->buf[B_CBRO].p; *cbr_total = c->cbr_total; }
+}
+
 // n coded pictures in payload slots -> the pictures of d_raw_out, whose format is fb: the coded pictures (fields 1), the
 // interleaved frames whose fields they are (fields 2, n / 2 frames), or -- drop > 0 -- the pictures at 1 / 2^drop size.
 // g: the geometry the level kernels run on; f: the sample format.  The arguments are the entry point's, checked there.
@@ -2408,19 +2431,7 @@ static int decode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_paylo
   if (!ld) {
     uint32_t *d_offs;
     const int32_t *d_cb = nullptr; const uint32_t *d_co = nullptr; uint64_t cbr_total = 0;
-    if (cp->mode == VC2HIP_HQ_CBR && cp->compressed_bytes > 0 && c->allow_cbr_index) { // the caller says CBR: the budgets predict the offsets
-      const int key[5] = {g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix};
-      if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
-        std::vector<int32_t> sb(ns);
-        int32_t *db; uint32_t *dof; uint64_t total;
-        if (vc2hip_slice_bytes(g.ys, g.xs, cp->compressed_bytes, cp->scalar, sb.data()) == VC2HIP_OK &&
-            cbr_offsets_upload(c, sb.data(), ns, cp->prefix, &db, &dof, &total) == VC2HIP_OK) {
-          memcpy(c->cbr_key, key, sizeof key);
-          c->cbr_total = total;
-        }
-      }
-      if (!memcmp(key, c->cbr_key, sizeof key)) { d_cb = (const int32_t *)c->buf[B_CBRB].p; d_co = (const uint32_t *)c->buf[B_CBRO].p; cbr_total = c->cbr_total; }
-    }
+    cbr_claim_tables(c, g, cp, &d_cb, &d_co, &cbr_total);
     if ((rc = build_index(c, (const uint8_t *)d_payload, (long long)payload_stride, (const unsigned long long *)d_lens, n, ns,
                           cp->prefix, cp->scalar, &d_offs, d_cb, d_co, cbr_total))) return rc;
     UnpackParams p;
@@ -2703,6 +2714,97 @@ static int decode_batch(vc2hip_ctx *c, const void *d_payload, size_t payload_str
 extern "C" int vc2hip_decode_batch_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens,
                                        int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, void *d_raw_out) {
   return decode_batch(c, d_payload, payload_stride, d_lens, n, f, cp, d_raw_out, cp && cp->mode == VC2HIP_LD);
+}
+
+// vc2hip_transcode_batch_dev (include/vc2hip.h): slots in, coarser slots out, through the coefficient
+// store and no further.  The decoder's slice index and slice reader leave the quantised coefficients in the store as
+// slice records; k_transcode_scale dequantises the slices that end at a coarser index; the encoder's slice coder
+// quantises and writes them (run_pack: every one of its forms, as encode_batch_common runs it).  No transform runs.
+// The capped form finds each picture's index first (transcode_measure / transcode_pick over the payload, two rounds).
+static int transcode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_in, size_t stride_in, const uint64_t *d_lens_in, int n,
+                                  const vc2hip_coding_params *cp, const vc2hip_transcode_params *tp, void *d_out, size_t stride_out,
+                                  uint64_t *d_lens_out, int32_t *d_qidx) {
+  ENTER(c);
+  int rc;
+  const int ns = g.ys * g.xs;
+  int32_t qm[VC2_MAX_BANDS];
+  if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
+  const bool s16 = use_store16(c, g, cp->kernel);
+  const long long sstride = (long long)ns * g.slice_coefs;
+  TranscodeParams p;
+  memset(&p, 0, sizeof p);
+  int32_t *d_store, *d_storew = nullptr, *d_q;
+  NEED(c, B_STORE, (size_t)n * sstride * 4, d_store);
+  if (s16) NEED(c, B_STOREW, (size_t)n * sstride * 4, d_storew);
+  NEED(c, B_QIDX, (size_t)n * ns * 4, d_q);
+  NEED(c, B_TCLEN, (size_t)n * ns * 4, p.qpack);
+  NEED(c, B_TCQ, (size_t)n * 4, p.qpic);
+  if (tp->cap_bytes > 0) NEED(c, B_CAPTAB, (size_t)n * VC2_CAP_ROW * 8, p.table);
+  uint32_t *d_offs;
+  const int32_t *d_cb = nullptr; const uint32_t *d_co = nullptr; uint64_t cbr_total = 0;
+  cbr_claim_tables(c, g, cp, &d_cb, &d_co, &cbr_total);
+  if ((rc = build_index(c, (const uint8_t *)d_in, (long long)stride_in, (const unsigned long long *)d_lens_in, n, ns, cp->prefix,
+                        cp->scalar, &d_offs, d_cb, d_co, cbr_total))) return rc;
+  UnpackParams u;
+  memset(&u, 0, sizeof u);
+  u.payload = (const uint8_t *)d_in; u.payload_stride = (long long)stride_in; u.lens = (const unsigned long long *)d_lens_in; u.offsets = d_offs;
+  u.store = d_store; u.store_stride = sstride; u.qidx = d_q;
+  u.store16 = s16; u.store_wide = d_storew;
+  u.n_slices = ns; u.slice_coefs = g.slice_coefs;
+  int n0[3];
+  fill_comp_arrays(g, u.comp_n, u.comp_off, n0);
+  u.prefix = cp->prefix; u.scalar = cp->scalar; u.err = c->d_err; u.xs = g.xs; u.stats = c->d_stat;
+  vc2_launch_unpack(c->L, u, n, c->stream);
+
+  p.in = u.payload; p.in_stride = u.payload_stride; p.in_lens = u.lens; p.in_offs = d_offs;
+  p.store = d_store; p.store_wide = d_storew; p.store16 = s16; p.store_stride = sstride;
+  p.slice_coefs = g.slice_coefs; p.qs = d_q; p.qidx_out = d_qidx;
+  p.n_slices = ns;
+  fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
+  p.prefix = cp->prefix; p.scalar = cp->scalar;
+  p.target = tp->q_index; p.capped = tp->cap_bytes > 0; p.cap = (unsigned long long)tp->cap_bytes;
+  p.qm_min = qm[0];
+  for (int b = 0; b < 3 * g.depth + 1; ++b) { p.qmatrix[b] = qm[b]; p.qm_min = std::min(p.qm_min, (int)qm[b]); }
+  p.err = c->d_err;
+  if (p.capped) {
+    HIPCHK(c, hipMemsetAsync(p.table, 0, (size_t)n * VC2_CAP_ROW * 8, c->stream));
+    for (p.round = 0; p.round < 2; ++p.round) {
+      vc2_launch_transcode_measure(c->L, p, n, c->stream);
+      vc2_launch_transcode_pick(c->L, p, n, c->stream);
+    }
+  }
+  vc2_launch_transcode_scale(c->L, p, n, c->stream);
+  return run_pack(c, g, n, d_store, p.qpack, qm, true, cp->prefix, cp->scalar, nullptr, nullptr, 0, (uint8_t *)d_out, (long long)stride_out,
+                  (unsigned long long *)d_lens_out, s16, d_storew);
+}
+
+extern "C" int vc2hip_transcode_batch_dev(vc2hip_ctx *c, const void *d_payload_in, size_t payload_stride_in, const uint64_t *d_lens_in,
+                                          int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
+                                          const vc2hip_transcode_params *tp, void *d_payload_out, size_t payload_stride_out,
+                                          uint64_t *d_lens_out, int32_t *d_qidx) {
+  if (int rc = batch_args(c, n, f, cp, payload_stride_in,
+                          {{d_payload_in, 16}, {d_lens_in, 8}, {d_payload_out, 16}, {d_lens_out, 8}, {d_qidx, 4, true}})) return rc;
+  if (!tp) return set_err(c, VC2HIP_EINVAL);
+  if (payload_stride_out & 15) return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_HQ_CAPPED)
+    return set_err(c, VC2HIP_EINVAL, "transcode_batch_dev: HQ pictures only");
+  if (tp->q_index < 0 || tp->q_index > VC2_CAP_Q_TOP || tp->cap_bytes < 0)
+    return set_err(c, VC2HIP_EINVAL, "transcode_batch_dev: q_index 0 .. 115, cap_bytes >= 0");
+  Geom g;
+  if (int rc = decode_check(c, f, cp, d_lens_in, false, g)) return rc;
+  const uint8_t *in8 = (const uint8_t *)d_payload_in, *out8 = (const uint8_t *)d_payload_out;
+  if (out8 < in8 + (size_t)n * payload_stride_in && in8 < out8 + (size_t)n * payload_stride_out)
+    return set_err(c, VC2HIP_EINVAL, "transcode_batch_dev: the output slots overlap the input slots");
+  // (the output is a VBR payload whatever coded the input: under an HQ_CBR cp the bound is still what three length bytes a
+  // slice can describe, not the budget -- slot bytes no encoder wrote may ask for all of it, and the slice coder clamps nothing)
+  if (payload_stride_out < vc2hip_max_payload_bytes(f, cp) || payload_stride_out < (size_t)g.ys * g.xs * max_slice_bytes(cp->prefix, cp->scalar))
+    return set_err(c, VC2HIP_ECAP);
+  const BatchBuf bufs[] = {{d_payload_in, payload_stride_in, false}, {d_lens_in, 8, false}, {d_payload_out, payload_stride_out, true},
+                           {d_lens_out, 8, true}, {d_qidx, (size_t)g.ys * g.xs * 4, true}};
+  return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    return transcode_batch_common(l, g, at[0], payload_stride_in, (const uint64_t *)at[1], count, cp, tp, at[2], payload_stride_out,
+                                  (uint64_t *)at[3], (int32_t *)at[4]);
+  });
 }
 
 // Pictures at 1 / 2^drop_levels size (include/vc2hip.h): f and cp are the CODED picture's; the split over lanes is by

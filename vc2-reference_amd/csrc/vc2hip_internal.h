@@ -517,6 +517,43 @@ struct SseParams {
 };
 void vc2_launch_squared_error(Launcher &L, const SseParams &p, int n_pictures, hipStream_t s);
 
+// Coded pictures to a coarser index without leaving the coefficient domain (vc2hip_transcode.hip;
+// vc2hip_transcode_batch_dev).  Slice s of picture i ends at max(its own index, q_i); a slice that
+// keeps its index keeps its coefficient values.  q_i is the call's target, or with a cap the smallest index of
+// target .. VC2_CAP_Q_TOP whose output is at most cap bytes, found in two rounds over the HQ_CAPPED table layout
+// (VC2_CAP_ROW words per picture; the table holds the sum of the components' bytes, the pick adds the slice headers).
+struct TranscodeParams {
+  const uint8_t *in;              // input slots
+  long long in_stride;
+  const unsigned long long *in_lens;
+  const uint32_t *in_offs;        // n_pictures * n_slices slice starts of the input (the decoder's slice index)
+  // the context's coefficient store after the decoder's slice reader: slice records, no band planes, no record heads
+  void *store;                    // int16_t (store16) or int32_t elements
+  int32_t *store_wide;            // store16: the escapes
+  int store16;
+  long long store_stride;         // per picture, elements
+  int slice_coefs, comp_off[3];
+  const int32_t *qs;              // n_pictures * n_slices: the input slices' indices, as the reader left them
+  int32_t *qpack;                 // n_pictures * n_slices: what the slice coder is handed (k_transcode_scale)
+  int32_t *qidx_out;              // n_pictures * n_slices: the indices the output slices carry; may be null
+  unsigned long long *table;      // capped: n_pictures * VC2_CAP_ROW, zero before the first round
+  int32_t *qpic;                  // capped: n_pictures chosen indices
+  int n_slices;
+  int comp_n[3], comp_n0[3];
+  int prefix, scalar;
+  int target;                     // tp->q_index
+  int capped;
+  unsigned long long cap;
+  int round;                      // measure / pick: 0 and 1, the two rounds of the capped search
+  int qmatrix[VC2_MAX_BANDS];
+  int qm_min;                     // the smallest matrix entry: a slice's index q is refused when q - qm_min > 119, as the decoder refuses it
+  unsigned *err;
+};
+void vc2_upload_tables_transcode(const QuantTables &t, hipStream_t s);
+void vc2_launch_transcode_measure(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
+void vc2_launch_transcode_pick(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
+void vc2_launch_transcode_scale(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
+
 // packed and semi-planar pictures <-> planar staging (vc2hip_packed.hip, vc2hip_set_packed_format)
 struct PackedParams {
   uint8_t *packed;            // the caller's buffer: picture 0's first v210 row / first row of its UV plane

@@ -1842,8 +1842,9 @@ __global__ __launch_bounds__(256) void k_hq_unpack(const UnpackParams p) {
 #endif
 constexpr int UNP_LUT_BITS = VC2_UNP_LUT_BITS, UNP_LUT_N = 1 << UNP_LUT_BITS;
 __device__ unsigned g_unp_lut[UNP_LUT_N];
-void vc2_upload_unpack_lut(hipStream_t s) {
-  // built once (contexts are created from several worker threads at a time: the copy below may still be reading it)
+// the table on the host (UNP_LUT_N entries): also what vc2hip_transcode.hip uploads for its own kernels
+const unsigned *vc2_unpack_lut_host() {
+  // built once (contexts are created from several worker threads at a time: a copy may still be reading it)
   static unsigned host[UNP_LUT_N];
   static std::once_flag once;
   std::call_once(once, [] {
@@ -1872,7 +1873,10 @@ void vc2_upload_unpack_lut(hipStream_t s) {
                               (unsigned)(val[0] & 0xFF) << 16 | (unsigned)(val[1] & 0xFF) << 24;
   }
   });
-  (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_unp_lut), host, sizeof host, 0, hipMemcpyHostToDevice, s);
+  return host;
+}
+void vc2_upload_unpack_lut(hipStream_t s) {
+  (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_unp_lut), vc2_unpack_lut_host(), UNP_LUT_N * sizeof(unsigned), 0, hipMemcpyHostToDevice, s);
 }
 
 // 33..64 unread bits at the top of `acc`; behind them a queue of up to four stream words in registers, and behind that

@@ -64,6 +64,11 @@ class PackedFormat(C.Structure):
                 ("plane_offset", C.c_size_t * 2), ("picture_stride", C.c_size_t)]
 
 
+class TranscodeParams(C.Structure):
+    """vc2hip_transcode_params: the target index and the optional per-picture byte cap of vc2hip_transcode_batch_dev"""
+    _fields_ = [("q_index", C.c_int), ("cap_bytes", C.c_int)]
+
+
 PACKING = {"none": 0, "v210": 1, "semiplanar": 2}   # VC2HIP_PACKING_*
 DWT_FAMILIES = ("tile", "fast", "stream", "pair", "plane")   # VC2HIP_DWT_TILE ... VC2HIP_DWT_PLANE
 
@@ -92,6 +97,7 @@ EXPORTS = [
     "vc2hip_encode_recon_batch_dev", "vc2hip_stream_write_fragments_dev",
     "vc2hip_set_sample_layout", "vc2hip_layout_picture_bytes",
     "vc2hip_set_packed_format", "vc2hip_packed_picture_bytes",
+    "vc2hip_transcode_batch_dev",
 ]
 
 
@@ -157,6 +163,8 @@ def load_library():
                                                     C.POINTER(CodingParams), C.c_int, vp]
     lib.vc2hip_encode_recon_batch_dev.argtypes = [vp, vp, C.c_int, C.POINTER(PictureFormat), C.POINTER(CodingParams),
                                                   vp, C.c_size_t, vp, vp, vp, vp]
+    lib.vc2hip_transcode_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat), C.POINTER(CodingParams),
+                                               C.POINTER(TranscodeParams), vp, C.c_size_t, vp, vp]
     lib.vc2hip_set_sample_layout.argtypes = [vp, C.POINTER(SampleLayout)]
     lib.vc2hip_layout_picture_bytes.argtypes = [C.POINTER(PictureFormat), C.POINTER(SampleLayout)]
     lib.vc2hip_layout_picture_bytes.restype = C.c_size_t
@@ -272,6 +280,12 @@ def coding_params(lib, fmt, kernel, depth, u, a, mode="HQ_ConstQ", q=0, s=0, pre
     if not ys or not xs:
         raise ValueError("The given waveletDepth, hSlice, and vSlice parameters cannot encode this input.")
     return CodingParams(KERNELS[kernel], depth, ys, xs, MODES[mode], q, s, prefix, scalar)
+
+
+def transcode_params(q_index, cap_bytes=0):
+    """a vc2hip_transcode_params: every slice ends at max(its own index, q_i); cap_bytes 0: q_i = q_index, else the smallest
+    index from q_index up whose output payload is at most cap_bytes"""
+    return TranscodeParams(q_index, cap_bytes)
 
 
 def psnr_db(sse, samples, bits):
@@ -501,6 +515,13 @@ class Vc2Hip:
     def encode_recon_batch_dev(self, d_raw, n, fmt, cp, d_payload=None, stride=0, d_lens=None, d_recon=None, d_sse=None, d_qidx=None):
         self._chk(self.lib.vc2hip_encode_recon_batch_dev(self.h, d_raw, n, C.byref(fmt), C.byref(cp), d_payload, stride, d_lens,
                                                          d_recon, d_sse, d_qidx))
+
+    # coded pictures to a coarser index, slots in and slots out (vc2hip_transcode_batch_dev): fmt and cp are the coded
+    # pictures', tp a transcode_params; d_qidx (n x slices int32: the output slices' indices) may be None
+    def transcode_batch_dev(self, d_in, stride_in, d_lens_in, n, fmt, cp, tp, d_out, stride_out, d_lens_out, d_qidx=None):
+        self._chk(self.lib.vc2hip_transcode_batch_dev(self.h, d_in, stride_in, d_lens_in, n, C.byref(fmt), C.byref(cp),
+                                                      C.byref(tp) if tp is not None else None, d_out, stride_out, d_lens_out,
+                                                      d_qidx))
 
     # interlaced frames as field pictures: frame_fmt is the frame's format, cp one field's; 2 * n_frames slots in stream order
     def encode_fields_batch_dev(self, d_frames, n_frames, frame_fmt, top_field_first, cp, d_payload, stride, d_lens):

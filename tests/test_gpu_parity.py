@@ -709,6 +709,80 @@ def test_multi_stream_ld_batches(oracle):
     hip.set_streams(1)
 
 
+def test_budget_tables_alternate_on_one_context(oracle):
+    """A context keeps ONE pair of per-slice budget tables on the device, keyed by (slices, bytes, scalar, prefix) with LD as
+    a key of its own.  LD and HQ_CBR coders, decoders, vc2hip_cbr_qindices (which overwrites the tables behind the key) and
+    the LD fragment writer take turns on a fresh context.  The HQ_CBR pictures share compressed_bytes with the LD ones and
+    differ in the key by scalar and prefix alone, and their budgets and offsets are not LD's (asserted below); the index
+    search is followed by the very key that was cached before it.  A turn that took the previous turn's tables would cut
+    its slices elsewhere: every payload, picture, index and stream is the oracle's, and no call leaves a device error."""
+    import torch
+    import vc2hip_py
+    from test_gpu_stream_dev import _seq_len
+    from test_gpu_stream_fragments import _frag, _result
+    hip = vc2hip_py.Vc2Hip(0)
+    w, h, depth, u, a, n, A, B = 128, 64, 2, 2, 4, 2, 4000, 3000   # 8 x 8 slices
+    raw = synth(w, h, "422", 10, 71, frames=n)
+    kinds = {"ld_a": dict(mode="LD", s=A), "ld_b": dict(mode="LD", s=B), "cbr_a": dict(mode="HQ_CBR", s=A, scalar=2, prefix=1)}
+    assert not np.array_equal(oracle.slice_bytes(8, 8, A, 2), oracle.slice_bytes(8, 8, A, 1))   # other budgets than LD's, and
+    # the prefix moves every offset: neither table of "cbr_a" serves "ld_a"
+    par = {k: make_params(w, h, "422", 10, "LeGall", depth, u, a, **kw) for k, kw in kinds.items()}
+    fmt = vc2hip_py.picture_format(w, h, "422", 10)
+    cps = {k: vc2hip_py.coding_params(hip.lib, fmt, "LeGall", depth, u, a, **kw) for k, kw in kinds.items()}
+    assert (cps["ld_a"].y_slices, cps["ld_a"].x_slices) == (8, 8)
+    rb = hip.raw_picture_bytes(fmt)
+    stride = max((hip.max_payload_bytes(fmt, cp) + 255) // 256 * 256 for cp in cps.values())
+    want = {}   # kind -> per picture (oracle stream, decoded picture)
+    for k, p in par.items():
+        want[k] = [_oracle_payload(oracle, p, raw[i * rb:(i + 1) * rb]) for i in range(n)]
+    d_raw = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda:0")
+    slots = {k: (torch.zeros(n * stride, dtype=torch.uint8, device="cuda:0"), torch.zeros(n, dtype=torch.int64, device="cuda:0"))
+             for k in kinds}
+    d_out = torch.zeros(n * rb, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+
+    def encode(kind):
+        d_pay, d_len = slots[kind]
+        d_pay.zero_()
+        torch.cuda.synchronize()
+        hip.encode_batch_dev(d_raw.data_ptr(), n, fmt, cps[kind], d_pay.data_ptr(), stride, d_len.data_ptr())
+        hip.sync()   # (raises on a device error)
+        pay = d_pay.cpu().numpy()
+        for i, length in enumerate(d_len.cpu().tolist()):
+            assert bytes(pay[i * stride:i * stride + length]) == want[kind][i][0][-13 - length:-13], (kind, i)
+
+    def decode(kind):
+        d_pay, d_len = slots[kind]
+        d_out.zero_()
+        torch.cuda.synchronize()
+        hip.decode_batch_dev(d_pay.data_ptr(), stride, d_len.data_ptr(), n, fmt, cps[kind], d_out.data_ptr())
+        hip.sync()
+        out = d_out.cpu().numpy().tobytes()
+        for i in range(n):
+            assert out[i * rb:(i + 1) * rb] == want[kind][i][1], (kind, i)
+
+    encode("ld_a")    # 1
+    encode("cbr_a")   # 2: the key differs from step 1's by scalar and prefix only
+    decode("cbr_a")   # 3
+    decode("ld_a")    # 4
+    encode("ld_b")    # 5
+    # 6: the index search of the fine-grained API uploads its caller's budgets (other ones) into the same buffer ...
+    y, uu, v = _planes(oracle, raw[:rb], w, h, "422", 10)
+    ty, tu, tv = (oracle.dwt_forward(pl, KERNELS["LeGall"], depth) for pl in (y, uu, v))
+    qm = oracle.quant_matrix(KERNELS["LeGall"], depth)
+    sb = oracle.slice_bytes(8, 8, 2800, 1)   # (below B: a coder that took these for its own would still stay inside its slots)
+    assert np.array_equal(hip.cbr_qindices(ty, tu, tv, depth, qm, sb, 1), oracle.cbr_qindices(ty, tu, tv, depth, qm, sb, 1))
+    encode("ld_b")    # ... and step 5's key, unchanged, must not vouch for them
+    encode("cbr_a")   # 7
+    # 8: the fragment writer cuts LD pictures by the LD budgets
+    flen = 700
+    stream = oracle.encode_stream(make_params(w, h, "422", 10, "LeGall", depth, u, a, fragment_length=flen, **kinds["ld_a"]), raw, n)
+    seq = _seq_len(stream)
+    got, _ = _result(hip, _frag(hip, slots["ld_a"][0], stride, slots["ld_a"][1], n, cps["ld_a"], flen, prev=seq))
+    assert got == stream[seq:]
+    hip.close()
+
+
 @pytest.mark.parametrize("scalar", [11, 30, 45])
 def test_large_slice_scalars(hip, oracle, scalar):
     """Slices that may exceed 8191 bytes use 32 KiB index chunks, beyond 32767 bytes a serial walk: any slice size

@@ -957,6 +957,22 @@ static void ll_layout(const Geom &g, int n, void *base, int elem_bytes, int32_t 
 }
 static void ll_layout(const Geom &g, int n, int32_t *base, LLPlanes &ll) { ll_layout(g, n, base, 4, nullptr, ll); }
 
+// A coefficient store of n pictures, as the transforms, the slice coders and the slice readers are handed it
+struct Store {
+  void *p;          // int32_t elements, or int16_t (s16) with ...
+  int32_t *wide;    // ... their wide elements (vc2hip_store.h); null for an int32 store
+  bool s16;
+  long long stride; // elements per picture: the slice records (record_stride), on the decoding side band planes and record heads behind them
+};
+static long long record_stride(const Geom &g) { return (long long)g.ys * g.xs * g.slice_coefs; }
+static Store records32(const Geom &g, int32_t *p) { return Store{p, nullptr, false, record_stride(g)}; } // (the fine-grained int32 calls)
+// The per-slice byte budgets of HQ_CBR and LD pictures on the device (budget_tables): one picture's worth, shared by the batch
+struct Budgets {
+  const int32_t *bytes; // per slice; null: no budgets (VBR)
+  const uint32_t *offs; // per slice: where it starts in the picture's payload
+  uint64_t total;       // the picture's payload bytes
+};
+
 // vc2hip_dwt_launches: one entry per transform launch, on the host where it is issued
 static void record_dwt(vc2hip_ctx *c, bool inverse, int level, int levels, int family, bool edge, bool s16, int segments, int tail,
                        bool small_gather, int n, int band_planes = 0) {
@@ -1003,15 +1019,16 @@ static void fill_level(LevelParams &p, const Geom &g, int level, int kernel, con
 }
 
 // forward transform of n pictures: raw words (first level fused) or int32 LL_0 planes (src_l: stride only) -> store
-// s16: 16-bit store and level planes with their wide planes (only with the fast kernels: use_store16)
+// st.s16: 16-bit store and level planes with their wide planes (only with the fast kernels: use_store16)
 static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const void *const src[3],
                        const RawPlane src_l[3], bool src_raw, const vc2hip_picture_format *f,
-                       void *store, const LLPlanes &ll, bool s16 = false, int32_t *store_wide = nullptr) {
+                       const Store &st, const LLPlanes &ll) {
+  const bool s16 = st.s16;
   auto level_params = [&](LevelParams &p, int level) {
     memset(&p, 0, sizeof p);
     fill_level(p, g, level, kernel, nullptr);
-    p.store = store; p.store_stride = (long long)g.ys * g.xs * g.slice_coefs;
-    p.store_wide = store_wide;
+    p.store = st.p; p.store_stride = st.stride;
+    p.store_wide = st.wide;
     p.err = c->d_err;
     p.ll_to_store = (level == g.depth - 1);
     const bool first = (level == 0) && src_raw;
@@ -1085,34 +1102,46 @@ static int run_forward(vc2hip_ctx *c, const Geom &g, int kernel, int n, const vo
 }
 
 // inverse transform of n pictures: store (optionally dequantised on load) -> int32 planes or raw words
-// bp: the decoder's band planes (levels < bp->levels read their bands from them; the store stride then includes them).
-// stream_mask != nullptr: a dry run -- nothing is launched, bit l of *stream_mask says whether level l would go through
-// the streaming kernel (the planning step of the band planes asks this before the slices are decoded).
-static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *store, const int32_t *qidx,
-                       const int32_t *qm, bool dequant, bool ll_ready, const LLPlanes &ll, void *const dst[3],
-                       const RawPlane *dst_l, bool dst_raw, const vc2hip_picture_format *f,
-                       bool s16 = false, int32_t *store_wide = nullptr, const BandPlanes *bp = nullptr,
-                       long long store_stride = 0, unsigned *stream_mask = nullptr, const HeadSplit *hs = nullptr, int head_level = 1 << 30,
-                       unsigned *fast_mask = nullptr, unsigned *tail_mask = nullptr, int norm_shift = 0, int level_base = 0) {
-  // norm_shift, level_base (reduced pictures, decode_batch_common): g is the picture the kept levels make; the launch that
-  // writes the raw words normalises by norm_shift bits, and the launch record counts levels in the CODED picture
-  if (tail_mask) *tail_mask = 0;
-  if (stream_mask) *stream_mask = 0;
-  if (fast_mask) *fast_mask = 0;
+struct InverseJob {
+  Store store;                    // (a dry run looks at s16 and the stride only)
+  const int32_t *qidx = nullptr;  // with qm: dequantise on load (null: the store holds coefficients)
+  const int32_t *qm = nullptr;
+  bool ll_ready = false;          // LD: the deepest LL planes are reconstructed already (ld_restore_ll), not read from the store
+  const BandPlanes *bp = nullptr; // the decoder's band planes: levels < bp->levels read their bands from them (the store stride then includes them)
+  const HeadSplit *hs = nullptr;  // the record heads, read by the levels from head_level on
+  int head_level = 1 << 30;
+  // reduced pictures (decode_batch_common): g is the picture the kept levels make; the launch that writes the raw words
+  // normalises by norm_shift bits, and the launch record counts levels in the CODED picture
+  int norm_shift = 0, level_base = 0;
+  void *const *dst = nullptr;     // level 0's output planes and how they lie; f null: int32 planes, else raw words of that format
+  const RawPlane *dst_l = nullptr;
+  const vc2hip_picture_format *f = nullptr;
+};
+// What a dry run of run_inverse finds, bit l for level l: the level would go through the streaming kernel, through its TAIL
+// instantiation, or -- not streaming -- through the fast tile kernel
+struct InversePlan { unsigned stream, fast, tail; };
+// plan != nullptr: a dry run -- nothing is launched (the planning step of the band planes and record heads asks before the
+// slices are decoded).
+static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, const InverseJob &job, const LLPlanes &ll, InversePlan *plan = nullptr) {
+  const bool s16 = job.store.s16, dst_raw = job.f != nullptr;
+  const RawPlane *const dst_l = job.dst_l;
+  const vc2hip_picture_format *const f = job.f;
+  const BandPlanes *const bp = job.bp;
+  if (plan) *plan = InversePlan{0, 0, 0};
   auto level_params = [&](LevelParams &p, int level) {
     memset(&p, 0, sizeof p);
-    fill_level(p, g, level, kernel, qm);
-    if (hs && level >= head_level) // the deep levels' coefficients live in the record heads (HeadSplit)
-      for (int k = 0; k < 3; ++k) if (g.c[k].ph) { p.rec_stride[k] = hs->n[k]; p.coef_off[k] = (int)hs->base[k]; }
-    p.store = store; p.store_stride = store_stride ? store_stride : (long long)g.ys * g.xs * g.slice_coefs;
+    fill_level(p, g, level, kernel, job.qm);
+    if (job.hs && level >= job.head_level) // the deep levels' coefficients live in the record heads (HeadSplit)
+      for (int k = 0; k < 3; ++k) if (g.c[k].ph) { p.rec_stride[k] = job.hs->n[k]; p.coef_off[k] = (int)job.hs->base[k]; }
+    p.store = job.store.p; p.store_stride = job.store.stride;
     for (int k = 0; k < 3; ++k) p.bp_base[k] = (bp && level < bp->levels && g.c[k].ph) ? bp->base[k][level] : -1;
     p.bp8 = bp && level < bp->levels && bp->bytes8;
-    p.store_wide = store_wide;
-    p.qidx = qidx; p.err = c->d_err; p.dequant = dequant;
-    p.ll_from_store = (level == g.depth - 1) && !ll_ready;
+    p.store_wide = job.store.wide;
+    p.qidx = job.qidx; p.err = c->d_err; p.dequant = job.qm != nullptr;
+    p.ll_from_store = (level == g.depth - 1) && !job.ll_ready;
     const bool fin = (level == 0) && dst_raw;
     for (int k = 0; k < 3; ++k) {
-      if (level == 0) { p.plane[k] = dst ? dst[k] : nullptr; p.plane_stride[k] = dst_l ? dst_l[k].stride : 0; }
+      if (level == 0) { p.plane[k] = job.dst ? job.dst[k] : nullptr; p.plane_stride[k] = dst_l ? dst_l[k].stride : 0; }
       else { p.plane[k] = ll.p[level][k]; p.plane_wide[k] = ll.w[level][k]; p.plane_stride[k] = ll.stride[level][k]; }
       p.ll[k] = ll.p[level + 1][k]; p.ll_wide[k] = ll.w[level + 1][k]; p.ll_stride[k] = ll.stride[level + 1][k];
     }
@@ -1126,7 +1155,7 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
       p.perm_wr = dst_l[0].le ? VC2_PERM_WR_LE : VC2_PERM_WR_BE;
       p.clip_lo = -(1 << (f->bit_depth - 1));
       p.clip_hi = (1 << (f->bit_depth - 1)) - 1;
-      p.norm_shift = norm_shift;
+      p.norm_shift = job.norm_shift;
     }
   };
   for (int level = g.depth - 1; level >= 0; --level) {
@@ -1134,7 +1163,7 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
     level_params(p, level);
     const bool fin = (level == 0) && dst_raw;
     // levels `level` and `level - 1` in one launch (vc2hip_dwt_pair.hip): the plane between them is never written
-    if (!stream_mask && !c->force_generic && c->allow_stream && c->allow_pair && level >= 1) {
+    if (!plan && !c->force_generic && c->allow_stream && c->allow_pair && level >= 1) {
       PairParams pp;
       memset(&pp, 0, sizeof pp);
       level_params(pp.a, level - 1);
@@ -1150,7 +1179,7 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
       if (lds) {
         int rc = vc2_launch_inverse_pair(c->L, kernel, fin_a, pp, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
-        record_dwt(c, true, level_base + level - 1, 2, VC2HIP_DWT_PAIR, fin_a, s16, pp.a.st_segmax, 0, false, n,
+        record_dwt(c, true, job.level_base + level - 1, 2, VC2HIP_DWT_PAIR, fin_a, s16, pp.a.st_segmax, 0, false, n,
                    std::max(band_plane_bits(pp.a), band_plane_bits(pp.b)));
         --level;
         continue;
@@ -1162,26 +1191,26 @@ static int run_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, void *st
       LevelParams ps = p;
       const size_t lds = vc2_stream_level_applicable(ps, kernel, fin, true, s16, n);
       if (lds) {
-        if (stream_mask) { *stream_mask |= 1u << level; if (tail_mask && ps.st_tail) *tail_mask |= 1u << level; continue; }
+        if (plan) { plan->stream |= 1u << level; if (ps.st_tail) plan->tail |= 1u << level; continue; }
         int rc = vc2_launch_inverse_stream(c->L, kernel, fin, ps, n, s16, lds, c->stream);
         if (rc) return set_err(c, rc, "invalid wavelet kernel");
-        record_dwt(c, true, level_base + level, 1, VC2HIP_DWT_STREAM, fin, s16, ps.st_segmax, ps.st_tail, false, n, band_plane_bits(ps));
+        record_dwt(c, true, job.level_base + level, 1, VC2HIP_DWT_STREAM, fin, s16, ps.st_segmax, ps.st_tail, false, n, band_plane_bits(ps));
         continue;
       }
     }
-    if (stream_mask) { if (fast_mask && !c->force_generic && vc2_fast_level_applicable(pf)) *fast_mask |= 1u << level; continue; }
+    if (plan) { if (!c->force_generic && vc2_fast_level_applicable(pf)) plan->fast |= 1u << level; continue; }
     if (bp && level < bp->levels) return set_err(c, VC2HIP_EINVAL, "internal: band planes without the streaming kernel");
     if (!c->force_generic && vc2_fast_level_applicable(pf)) {
       int rc = vc2_launch_inverse_fast(c->L, kernel, fin, pf, n, s16, c->stream);
       if (rc) return set_err(c, rc, "invalid wavelet kernel");
-      record_dwt(c, true, level_base + level, 1, VC2HIP_DWT_FAST, fin, s16, 0, 0, vc2_fast_small_gather(pf), n, band_plane_bits(pf));
+      record_dwt(c, true, job.level_base + level, 1, VC2HIP_DWT_FAST, fin, s16, 0, 0, vc2_fast_small_gather(pf), n, band_plane_bits(pf));
       continue;
     }
     if (s16) return set_err(c, VC2HIP_EINVAL, "internal: 16-bit store without the fast level kernels");
     if (vc2_level_lds_bytes(kernel, p) > 160 * 1024) return set_err(c, VC2HIP_EINVAL, "slice too large for one LDS tile");
     int rc = vc2_launch_inverse_level(c->L, kernel, fin, p, n, c->stream);
     if (rc) return set_err(c, rc, "invalid wavelet kernel");
-    record_dwt(c, true, level_base + level, 1, VC2HIP_DWT_TILE, fin, false, 0, 0, false, n, band_plane_bits(p));
+    record_dwt(c, true, job.level_base + level, 1, VC2HIP_DWT_TILE, fin, false, 0, 0, false, n, band_plane_bits(p));
   }
   return VC2HIP_OK;
 }
@@ -1290,27 +1319,36 @@ static void fill_comp_arrays(const Geom &g, int n[3], int off[3], int n0[3]) {
   for (int c = 0; c < 3; ++c) { n[c] = g.c[c].sh * g.c[c].sw; off[c] = g.c[c].coef_off; n0[c] = g.c[c].n0 ? g.c[c].n0 : 1; }
 }
 
-// pack n pictures from the store into d_payload; VBR goes through slots + scan + compaction
-static int run_pack(vc2hip_ctx *c, const Geom &g, int n, const void *store, const int32_t *d_qidx,
-                    const int32_t *qm, bool quantise, int prefix, int scalar, const int32_t *d_cbr_bytes,
-                    const uint32_t *d_cbr_offs, uint64_t cbr_total, uint8_t *d_payload, long long stride,
-                    unsigned long long *d_lens, bool s16 = false, const int32_t *store_wide = nullptr) {
+struct PackJob {
+  Store store;
+  const int32_t *qidx;         // n x slices
+  const int32_t *qm = nullptr; // null: the store holds quantised values already (the fine-grained API)
+  int prefix, scalar;
+  Budgets budgets = {};        // HQ_CBR; none: VBR
+  uint8_t *payload;            // the slots, their stride and their lengths
+  long long stride;
+  unsigned long long *lens;
+};
+// pack n pictures from the store into the job's payload slots; VBR goes through slots + scan + compaction
+static int run_pack(vc2hip_ctx *c, const Geom &g, int n, const PackJob &job) {
   const int ns = g.ys * g.xs;
+  const int prefix = job.prefix, scalar = job.scalar;
+  const int32_t *const d_cbr_bytes = job.budgets.bytes;
   PackParams p;
   memset(&p, 0, sizeof p);
-  p.store = store; p.store_stride = (long long)ns * g.slice_coefs;
-  p.store16 = s16; p.store_wide = store_wide;
-  p.qidx = d_qidx; p.n_slices = ns; p.slice_coefs = g.slice_coefs;
+  p.store = job.store.p; p.store_stride = job.store.stride;
+  p.store16 = job.store.s16; p.store_wide = job.store.wide;
+  p.qidx = job.qidx; p.n_slices = ns; p.slice_coefs = g.slice_coefs;
   fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
   p.depth = g.depth; p.prefix = prefix; p.scalar = scalar;
-  for (int b = 0; b < 3 * g.depth + 1; ++b) p.qmatrix[b] = qm ? qm[b] : 0;
-  p.err = c->d_err; p.quantise = quantise;
-  p.payload = d_payload; p.payload_stride = stride;
+  for (int b = 0; b < 3 * g.depth + 1; ++b) p.qmatrix[b] = job.qm ? job.qm[b] : 0;
+  p.err = c->d_err; p.quantise = job.qm != nullptr;
+  p.payload = job.payload; p.payload_stride = job.stride;
   const bool gimg = vc2_pack_image_mode(prefix, scalar) < 0; // slice images in the slots (global memory): CBR goes through slots too
   if (d_cbr_bytes && !gimg) {
-    p.cbr_bytes = d_cbr_bytes; p.cbr_offsets = d_cbr_offs;
+    p.cbr_bytes = d_cbr_bytes; p.cbr_offsets = job.budgets.offs;
     vc2_launch_pack(c->L, p, n, c->stream);
-    vc2_launch_fill_u64(c->L, d_lens, cbr_total, (size_t)n, c->stream);
+    vc2_launch_fill_u64(c->L, job.lens, job.budgets.total, (size_t)n, c->stream);
     return VC2HIP_OK;
   }
   // single pass: slice offsets by decoupled look-back inside the pack kernel -- the default where k_hq_pack16 codes the
@@ -1326,7 +1364,7 @@ static int run_pack(vc2hip_ctx *c, const Geom &g, int n, const void *store, cons
     NEED(c, B_SIZES, (size_t)n * lb_stride * 8, lb);
     HIPCHK(c, hipMemsetAsync(lb, 0, (size_t)n * lb_stride * 8, c->stream));
     vc2_prof_break(c->L);
-    p.lookback = lb; p.lookback_stride = lb_stride; p.lens = d_lens;
+    p.lookback = lb; p.lookback_stride = lb_stride; p.lens = job.lens;
     vc2_launch_pack(c->L, p, n, c->stream);
     return VC2HIP_OK;
   }
@@ -1343,7 +1381,7 @@ static int run_pack(vc2hip_ctx *c, const Geom &g, int n, const void *store, cons
   NEED(c, B_SIZES, (size_t)n * ns * 4, sizes);
   NEED(c, B_OFFS, (size_t)n * ns * 4, offs);
   p.slots = slots; p.slot_bytes = slot; p.sizes = sizes;
-  if (d_cbr_bytes) { p.cbr_bytes = d_cbr_bytes; p.cbr_offsets = d_cbr_offs; }
+  if (d_cbr_bytes) { p.cbr_bytes = d_cbr_bytes; p.cbr_offsets = job.budgets.offs; }
   // VBR with several slices per wavefront of the packer (slices of up to 256 + 2 x 128 coefficients: HD pictures): the
   // slices of a pack workgroup share a slot, back to back -- sizes, offsets and the compaction are per workgroup (a
   // sixteenth or an eighth of the entries and copies, each as many times as long).  32 HD pictures: pack 0.221 -> 0.227 ms
@@ -1355,12 +1393,12 @@ static int run_pack(vc2hip_ctx *c, const Geom &g, int n, const void *store, cons
   vc2_launch_pack(c->L, p, n, c->stream);
   if (spt) {
     const int nt = (ns + spt - 1) / spt;
-    vc2_launch_scan_sizes(c->L, sizes, offs, d_lens, nt, n, c->stream);
-    vc2_launch_compact(c->L, slots, spt * slot, sizes, offs, d_payload, stride, nt, n, c->stream);
+    vc2_launch_scan_sizes(c->L, sizes, offs, job.lens, nt, n, c->stream);
+    vc2_launch_compact(c->L, slots, spt * slot, sizes, offs, job.payload, job.stride, nt, n, c->stream);
     return VC2HIP_OK;
   }
-  vc2_launch_scan_sizes(c->L, sizes, offs, d_lens, ns, n, c->stream); // (CBR: the same offsets as d_cbr_offs; sizes = budgets)
-  vc2_launch_compact(c->L, slots, slot, sizes, offs, d_payload, stride, ns, n, c->stream);
+  vc2_launch_scan_sizes(c->L, sizes, offs, job.lens, ns, n, c->stream); // (CBR: the same offsets as the budgets'; sizes = budgets)
+  vc2_launch_compact(c->L, slots, slot, sizes, offs, job.payload, job.stride, ns, n, c->stream);
   return VC2HIP_OK;
 }
 
@@ -1395,7 +1433,7 @@ extern "C" int vc2hip_dwt_forward(vc2hip_ctx *c, const int32_t *in, int h, int w
   HIPCHK(c, hipMemcpyAsync(d_plane, padded.data(), pb, hipMemcpyHostToDevice, c->stream));
   const void *src[3] = {d_plane, nullptr, nullptr};
   const RawPlane ss[3] = {{(long long)ph * pw, 0, 0, 0}, {}, {}};
-  rc = run_forward(c, g, kernel, 1, src, ss, false, nullptr, d_store, ll);
+  rc = run_forward(c, g, kernel, 1, src, ss, false, nullptr, records32(g, d_store), ll);
   if (rc) return rc;
   vc2_launch_store_to_plane(c->L, d_store, g.slice_coefs, 0, d_plane, ph, pw, depth, g.ys, g.xs, nullptr, nullptr, 0,
                             c->d_err, c->stream);
@@ -1423,7 +1461,10 @@ extern "C" int vc2hip_dwt_inverse(vc2hip_ctx *c, const int32_t *in, int ph, int 
   vc2_launch_plane_to_store(c->L, d_plane, ph, pw, depth, g.ys, g.xs, d_store, g.slice_coefs, 0, c->stream);
   void *dst[3] = {d_plane, nullptr, nullptr};
   const RawPlane ds[3] = {{(long long)ph * pw, 0, 0, 0}, {}, {}};
-  rc = run_inverse(c, g, kernel, 1, d_store, nullptr, nullptr, false, false, ll, dst, ds, false, nullptr);
+  InverseJob job; // (coefficients in, int32 samples out: no matrix, no raw words)
+  job.store = records32(g, d_store);
+  job.dst = dst; job.dst_l = ds;
+  rc = run_inverse(c, g, kernel, 1, job, ll);
   if (rc) return rc;
   std::vector<int32_t> full((size_t)ph * pw);
   HIPCHK(c, hipMemcpyAsync(full.data(), d_plane, pb, hipMemcpyDeviceToHost, c->stream));
@@ -1524,19 +1565,39 @@ static int store_to_planes(vc2hip_ctx *c, const Geom &g, const int32_t *d_store,
   return VC2HIP_OK;
 }
 
-static int cbr_offsets_upload(vc2hip_ctx *c, const int32_t *bytes, int ns, int prefix, int32_t **d_b, uint32_t **d_o, uint64_t *total) {
-  c->cbr_key[0] = -1; // whatever was cached is overwritten
-  std::vector<uint32_t> offs(ns);
-  uint64_t run = 0;
-  for (int i = 0; i < ns; ++i) { offs[i] = (uint32_t)run; run += (uint64_t)bytes[i] + prefix; }
-  *total = run;
-  int32_t *db; uint32_t *dof;
-  NEED(c, B_CBRB, (size_t)ns * 4, db);
-  NEED(c, B_CBRO, (size_t)ns * 4, dof);
-  HIPCHK(c, hipMemcpyAsync(db, bytes, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dof, offs.data(), (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *d_b = db; *d_o = dof;
+// The one owner of the context's budget tables (B_CBRB, B_CBRO, cbr_total) and of the key that says what they hold.
+// HQ_CBR: the budgets of vc2hip_slice_bytes(ys, xs, compressed_bytes, scalar), each slice `prefix` bytes behind the one before.
+// LD: scalar 1 and prefix LD_BUDGETS (EncodeStream.cpp:509-512, DecodeStream.cpp:312, :331-333) -- the offsets carry no prefix.
+// Both are uploaded only when the key differs from the cached one or the buffer is gone: no copy and no wait in any later call.
+// given: the caller's own budgets (the fine-grained int32 entry points; compressed_bytes and scalar are not looked at): always
+// uploaded, and the cache is left invalid.  The key returns only behind a complete upload, so a failure on the way (an
+// allocation, a copy) leaves no mode another mode's tables.  vc2hip_slice_bytes refuses ys, xs or scalar below 1 and nothing
+// else; every caller's entry checks hold all three (make_geom / stream_cp_ok, encode_check / decode_check; LD passes 1).
+enum { LD_BUDGETS = -7 };
+static int budget_tables(vc2hip_ctx *c, int ys, int xs, int compressed_bytes, int scalar, int prefix, Budgets &b, const int32_t *given = nullptr) {
+  const int ns = ys * xs;
+  const int key[5] = {ys, xs, compressed_bytes, scalar, prefix};
+  if (given || memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
+    c->cbr_key[0] = -1; // whatever was cached is overwritten
+    std::vector<int32_t> made;
+    if (!given) {
+      made.resize(ns);
+      if (int rc = vc2hip_slice_bytes(ys, xs, compressed_bytes, scalar, made.data())) return set_err(c, rc);
+    }
+    const int32_t *bytes = given ? given : made.data();
+    std::vector<uint32_t> offs(ns);
+    uint64_t run = 0;
+    for (int i = 0; i < ns; ++i) { offs[i] = (uint32_t)run; run += (uint64_t)bytes[i] + (prefix == LD_BUDGETS ? 0 : prefix); }
+    int32_t *db; uint32_t *dof;
+    NEED(c, B_CBRB, (size_t)ns * 4, db);
+    NEED(c, B_CBRO, (size_t)ns * 4, dof);
+    HIPCHK(c, hipMemcpyAsync(db, bytes, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dof, offs.data(), (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the tables live on this function's stack)
+    c->cbr_total = run;
+    if (!given) memcpy(c->cbr_key, key, sizeof key);
+  }
+  b = Budgets{(const int32_t *)c->buf[B_CBRB].p, (const uint32_t *)c->buf[B_CBRO].p, c->cbr_total};
   return VC2HIP_OK;
 }
 
@@ -1557,14 +1618,16 @@ extern "C" int vc2hip_hq_pack(vc2hip_ctx *c, const int32_t *y, const int32_t *u,
   if ((rc = planes_to_store(c, g, pl, d_store))) return rc;
   HIPCHK(c, hipMemcpyAsync(d_q, qidx, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
   size_t paycap = (size_t)ns * max_slice_bytes(prefix, scalar);
-  int32_t *d_cb = nullptr; uint32_t *d_co = nullptr; uint64_t total = 0;
+  PackJob job; // (no matrix: the planes are quantised)
   if (cbr) {
-    if ((rc = cbr_offsets_upload(c, cbr, ns, prefix, &d_cb, &d_co, &total))) return rc;
-    paycap = total;
+    if ((rc = budget_tables(c, g.ys, g.xs, 0, scalar, prefix, job.budgets, cbr))) return rc;
+    paycap = job.budgets.total;
   }
   NEED(c, B_PAYLOAD, paycap + 64, d_pay);
-  rc = run_pack(c, g, 1, d_store, d_q, nullptr, false, prefix, scalar, d_cb, d_co, total, d_pay, (long long)paycap, d_len);
-  if (rc) return rc;
+  job.store = records32(g, d_store);
+  job.qidx = d_q; job.prefix = prefix; job.scalar = scalar;
+  job.payload = d_pay; job.stride = (long long)paycap; job.lens = d_len;
+  if ((rc = run_pack(c, g, 1, job))) return rc;
   unsigned long long len = 0;
   HIPCHK(c, hipMemcpyAsync(&len, d_len, 8, hipMemcpyDeviceToHost, c->stream));
   if ((rc = vc2hip_sync(c))) return rc;
@@ -1575,26 +1638,51 @@ extern "C" int vc2hip_hq_pack(vc2hip_ctx *c, const int32_t *y, const int32_t *u,
 }
 
 // slice offsets of one VBR payload already on the device
-// cbr_budget / cbr_offs / cbr_total (device tables of the HQ_CBR slice budgets, or null): the offsets are first claimed
-// from the budgets and checked against the stream (vc2_launch_cbr_index); the general index only works if that fails
+// claim (the HQ_CBR slice budgets, or none): the offsets are first claimed from the budgets and checked against the
+// stream (vc2_launch_cbr_index); the general index only works if that fails
 static int build_index(vc2hip_ctx *c, const uint8_t *d_pay, long long stride, const unsigned long long *d_lens, int n, int ns,
-                       int prefix, int scalar, uint32_t **d_offs_out, const int32_t *cbr_budget = nullptr,
-                       const uint32_t *cbr_offs = nullptr, uint64_t cbr_total = 0) {
+                       int prefix, int scalar, uint32_t **d_offs_out, const Budgets &claim = Budgets{}) {
   uint32_t *d_offs; void *ws;
   NEED(c, B_OFFS, (size_t)n * ns * 4, d_offs);
   const size_t wsb = vc2_slice_index_workspace(n, (size_t)stride, prefix, scalar);
   NEED(c, B_INDEX, wsb, ws);
   HIPCHK(c, hipMemsetAsync(d_offs, 0xFF, (size_t)n * ns * 4, c->stream)); // unreachable slices read past the payload
   unsigned *bad = nullptr;
-  if (cbr_budget && c->allow_cbr_index) {
+  if (claim.bytes && c->allow_cbr_index) {
     bad = (unsigned *)((char *)c->d_err + 64); // (the error word's block: 256 bytes, the LD tables behind them)
     HIPCHK(c, hipMemsetAsync(bad, 0, sizeof(unsigned), c->stream));
   }
   vc2_prof_break(c->L);
-  if (bad) vc2_launch_cbr_index(c->L, d_pay, stride, d_lens, cbr_budget, cbr_offs, cbr_total, d_offs, ns, prefix, scalar, n, bad, c->stream);
+  if (bad) vc2_launch_cbr_index(c->L, d_pay, stride, d_lens, claim.bytes, claim.offs, claim.total, d_offs, ns, prefix, scalar, n, bad, c->stream);
   vc2_launch_slice_index(c->L, d_pay, stride, d_lens, d_offs, ns, prefix, scalar, n, c->d_err, c->stream, ws, wsb, bad);
   *d_offs_out = d_offs;
   return VC2HIP_OK;
+}
+
+// The HQ slice reader's job.  Band planes, record heads, xs and the statistics word are the batch decoders' to add.
+static void fill_unpack(UnpackParams &p, const Geom &g, const uint8_t *d_pay, long long stride, const unsigned long long *d_lens,
+                        const uint32_t *d_offs, const Store &st, int32_t *d_q, int prefix, int scalar, unsigned *err) {
+  memset(&p, 0, sizeof p);
+  p.payload = d_pay; p.payload_stride = stride; p.lens = d_lens; p.offsets = d_offs;
+  p.store = st.p; p.store_stride = st.stride; p.qidx = d_q;
+  p.store16 = st.s16; p.store_wide = st.wide;
+  p.n_slices = g.ys * g.xs; p.slice_coefs = g.slice_coefs;
+  int n0[3];
+  fill_comp_arrays(g, p.comp_n, p.comp_off, n0);
+  p.prefix = prefix; p.scalar = scalar; p.err = err;
+}
+// The HQ_CBR index search's job (HQ_CAPPED measures with the same: CapParams::s); d_sb: the slice budgets
+static void fill_cbr(CbrParams &p, const Geom &g, const Store &st, int32_t *d_q, const int32_t *d_sb, int scalar, const int32_t *qm,
+                     bool general_only, unsigned *err) {
+  memset(&p, 0, sizeof p);
+  p.store = st.p; p.store_stride = st.stride; p.qidx = d_q; p.slice_bytes = d_sb;
+  p.store16 = st.s16; p.store_wide = st.wide;
+  p.n_slices = g.ys * g.xs; p.slice_coefs = g.slice_coefs;
+  fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
+  p.scalar = scalar; p.err = err;
+  p.general_only = general_only;
+  p.n_bands = 3 * g.depth + 1;
+  for (int b = 0; b < p.n_bands; ++b) p.qmatrix[b] = qm[b];
 }
 
 extern "C" int vc2hip_hq_unpack(vc2hip_ctx *c, const uint8_t *in, size_t len, const vc2hip_geom *ga, int prefix, int scalar,
@@ -1616,13 +1704,7 @@ extern "C" int vc2hip_hq_unpack(vc2hip_ctx *c, const uint8_t *in, size_t len, co
   HIPCHK(c, hipMemcpyAsync(d_len, &l64, 8, hipMemcpyHostToDevice, c->stream));
   if ((rc = build_index(c, d_pay, (long long)stride, d_len, 1, ns, prefix, scalar, &d_offs))) return rc;
   UnpackParams p;
-  memset(&p, 0, sizeof p);
-  p.payload = d_pay; p.payload_stride = (long long)stride; p.lens = d_len; p.offsets = d_offs;
-  p.store = d_store; p.store_stride = (long long)ns * g.slice_coefs; p.qidx = d_q;
-  p.n_slices = ns; p.slice_coefs = g.slice_coefs;
-  int n0[3];
-  fill_comp_arrays(g, p.comp_n, p.comp_off, n0);
-  p.prefix = prefix; p.scalar = scalar; p.err = c->d_err;
+  fill_unpack(p, g, d_pay, (long long)stride, d_len, d_offs, records32(g, d_store), d_q, prefix, scalar, c->d_err);
   vc2_launch_unpack(c->L, p, 1, c->stream);
   int32_t *pl[3] = {y, u, v};
   if ((rc = store_to_planes(c, g, d_store, pl))) return rc;
@@ -1646,42 +1728,45 @@ extern "C" int vc2hip_cbr_qindices(vc2hip_ctx *c, const int32_t *y, const int32_
   int rc = geom_from_abi(g, ga);
   if (rc) return set_err(c, rc);
   const int ns = g.ys * g.xs;
-  int32_t *d_store, *d_q, *d_sb;
+  int32_t *d_store, *d_q;
   NEED(c, B_STORE, (size_t)ns * g.slice_coefs * 4, d_store);
   NEED(c, B_QIDX, (size_t)ns * 4, d_q);
-  NEED(c, B_CBRB, (size_t)ns * 4, d_sb);
-  c->cbr_key[0] = -1;
   const int32_t *pl[3] = {y, u, v};
   if ((rc = planes_to_store(c, g, pl, d_store))) return rc;
-  HIPCHK(c, hipMemcpyAsync(d_sb, slice_bytes, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+  Budgets b; // (the search reads the bytes alone; the offsets are uploaded beside them only because the owner keeps the pair whole)
+  if ((rc = budget_tables(c, g.ys, g.xs, 0, scalar, 0, b, slice_bytes))) return rc;
   CbrParams p;
-  memset(&p, 0, sizeof p);
-  p.store = d_store; p.store_stride = (long long)ns * g.slice_coefs; p.qidx = d_q; p.slice_bytes = d_sb;
-  p.n_slices = ns; p.slice_coefs = g.slice_coefs;
-  fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
-  p.scalar = scalar; p.err = c->d_err;
-  p.general_only = c->cbr_general;
-  for (int b = 0; b < 3 * g.depth + 1; ++b) p.qmatrix[b] = qm[b];
-  p.n_bands = 3 * g.depth + 1;
+  fill_cbr(p, g, records32(g, d_store), d_q, b.bytes, scalar, qm, c->cbr_general, c->d_err);
   vc2_launch_cbr(c->L, p, 1, c->stream);
   HIPCHK(c, hipMemcpyAsync(qidx, d_q, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
   return vc2hip_sync(c);
 }
 
-static int ld_offsets_upload(vc2hip_ctx *c, const int32_t *bytes, int ns, int32_t **d_b, uint32_t **d_o, uint64_t *total) {
-  return cbr_offsets_upload(c, bytes, ns, 0, d_b, d_o, total);
-}
-
-static void fill_ld_unpack(LdUnpackParams &p, const Geom &g, const uint8_t *d_pay, long long stride, const int32_t *d_sb,
-                           const uint32_t *d_so, int32_t *d_store, int32_t *d_q, unsigned *err) {
+static void fill_ld_unpack(LdUnpackParams &p, const Geom &g, const uint8_t *d_pay, long long stride, const Budgets &b,
+                           const Store &st, int32_t *d_q, unsigned *err) { // (LD stores are int32 throughout)
   memset(&p, 0, sizeof p);
-  const int ns = g.ys * g.xs;
-  p.payload = d_pay; p.payload_stride = stride; p.slice_bytes = d_sb; p.offsets = d_so;
-  p.store = d_store; p.store_stride = (long long)ns * g.slice_coefs; p.qidx = d_q;
-  p.n_slices = ns; p.slice_coefs = g.slice_coefs;
+  p.payload = d_pay; p.payload_stride = stride; p.slice_bytes = b.bytes; p.offsets = b.offs;
+  p.store = (int32_t *)st.p; p.store_stride = st.stride; p.qidx = d_q;
+  p.n_slices = g.ys * g.xs; p.slice_coefs = g.slice_coefs;
   int n0[3];
   fill_comp_arrays(g, p.comp_n, p.comp_off, n0);
   p.err = err;
+}
+
+// LD: the quantised LL residuals of n pictures' slice records -> the DC-predicted, reconstructed LL planes of the deepest
+// level (Quantisation.cpp:287-306).  One launch for the three components, or one each where a plane does not fit in LDS.
+static void ld_restore_ll(vc2hip_ctx *c, const Geom &g, int n, const Store &st, const int32_t *d_q, int qm0, const LLPlanes &ll) {
+  LdLl3Params lp;
+  lp.store = (const int32_t *)st.p; lp.store_stride = st.stride; lp.slice_coefs = g.slice_coefs;
+  lp.ys = g.ys; lp.xs = g.xs; lp.qidx = d_q; lp.qm0 = qm0; lp.err = c->d_err;
+  for (int k = 0; k < 3; ++k) {
+    lp.coef_off[k] = g.c[k].coef_off; lp.llh[k] = g.c[k].ph >> g.depth; lp.llw[k] = g.c[k].pw >> g.depth;
+    lp.ll_plane[k] = (int32_t *)ll.p[g.depth][k]; lp.ll_stride[k] = ll.stride[g.depth][k];
+  }
+  if (vc2_launch_ld_ll3(c->L, lp, n, c->stream)) return;
+  for (int k = 0; k < 3; ++k)
+    vc2_launch_ld_ll(c->L, lp.store, lp.store_stride, g.slice_coefs, g.c[k].coef_off, g.c[k].n0, lp.llh[k], lp.llw[k], g.ys, g.xs, d_q, qm0,
+                     lp.ll_plane[k], lp.ll_stride[k], n, c->d_err, c->stream);
 }
 
 extern "C" int vc2hip_ld_unpack(vc2hip_ctx *c, const uint8_t *in, size_t len, const vc2hip_geom *ga, const int32_t *slice_bytes,
@@ -1692,33 +1777,32 @@ extern "C" int vc2hip_ld_unpack(vc2hip_ctx *c, const uint8_t *in, size_t len, co
   int rc = geom_from_abi(g, ga);
   if (rc) return set_err(c, rc);
   const int ns = g.ys * g.xs;
-  int32_t *d_store, *d_q, *d_sb; uint32_t *d_so; uint8_t *d_pay; uint64_t total;
+  int32_t *d_store, *d_q; uint8_t *d_pay; Budgets b;
   NEED(c, B_STORE, (size_t)ns * g.slice_coefs * 4, d_store);
   NEED(c, B_QIDX, (size_t)ns * 4, d_q);
-  if ((rc = ld_offsets_upload(c, slice_bytes, ns, &d_sb, &d_so, &total))) return rc;
-  if (total > len) return set_err(c, VC2HIP_ESTREAM);
+  if ((rc = budget_tables(c, g.ys, g.xs, 0, 1, LD_BUDGETS, b, slice_bytes))) return rc;
+  if (b.total > len) return set_err(c, VC2HIP_ESTREAM);
   NEED(c, B_PAYLOAD, len + 64, d_pay);
   HIPCHK(c, hipMemcpyAsync(d_pay, in, len, hipMemcpyHostToDevice, c->stream));
   LdUnpackParams p;
-  fill_ld_unpack(p, g, d_pay, (long long)len, d_sb, d_so, d_store, d_q, c->d_err);
+  fill_ld_unpack(p, g, d_pay, (long long)len, b, records32(g, d_store), d_q, c->d_err);
   vc2_launch_ld_unpack(c->L, p, 1, c->stream);
   int32_t *pl[3] = {y, u, v};
   if ((rc = store_to_planes(c, g, d_store, pl))) return rc;
   HIPCHK(c, hipMemcpyAsync(qidx, d_q, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
-  if (consumed) *consumed = (size_t)total;
+  if (consumed) *consumed = (size_t)b.total;
   return vc2hip_sync(c);
 }
 
 // ------------------------------------------------------------------------------------------
 // LD encode
 // ------------------------------------------------------------------------------------------
-static int fill_ld_enc(vc2hip_ctx *c, LdEncParams &p, const Geom &g, int32_t *d_store, int32_t *d_q, const int32_t *qm,
-                       const LLPlanes &ll, const int32_t *d_sb, const uint32_t *d_so, int max_slice, uint8_t *d_pay,
-                       long long stride) {
+static int fill_ld_enc(vc2hip_ctx *c, LdEncParams &p, const Geom &g, const Store &st, int32_t *d_q, const int32_t *qm,
+                       const LLPlanes &ll, const Budgets &b, int max_slice, uint8_t *d_pay, long long stride) {
   memset(&p, 0, sizeof p);
   const int ns = g.ys * g.xs;
-  p.store = d_store; p.store_stride = (long long)ns * g.slice_coefs; p.qidx = d_q;
-  p.slice_bytes = d_sb; p.offsets = d_so;
+  p.store = (int32_t *)st.p; p.store_stride = st.stride; p.qidx = d_q;
+  p.slice_bytes = b.bytes; p.offsets = b.offs;
   for (int k = 0; k < 3; ++k) {
     p.restored[k] = (int32_t *)ll.p[g.depth][k]; p.restored_stride[k] = ll.stride[g.depth][k];
     p.ll_w[k] = g.c[k].pw >> g.depth;
@@ -1765,7 +1849,7 @@ extern "C" int vc2hip_quantise_ld(vc2hip_ctx *c, const int32_t *coef, int ph, in
   HIPCHK(c, hipMemcpyAsync(d_q, qidx, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
   vc2_launch_plane_to_store(c->L, d_plane, ph, pw, depth, ys, xs, d_store, g.slice_coefs, 0, c->stream);
   LdEncParams p;
-  if ((rc = fill_ld_enc(c, p, g, d_store, d_q, qm, ll, nullptr, nullptr, 0, nullptr, 0))) return rc;
+  if ((rc = fill_ld_enc(c, p, g, records32(g, d_store), d_q, qm, ll, Budgets{}, 0, nullptr, 0))) return rc;
   p.search = 0;
   vc2_launch_ld_quantise(c->L, p, 1, c->stream);
   vc2_launch_store_to_plane(c->L, d_store, g.slice_coefs, 0, d_plane, ph, pw, depth, ys, xs, nullptr, nullptr, 0, c->d_err, c->stream);
@@ -1782,7 +1866,7 @@ extern "C" int vc2hip_ld_qindices(vc2hip_ctx *c, const int32_t *y, const int32_t
   int rc = geom_from_abi(g, ga);
   if (rc) return set_err(c, rc);
   const int ns = g.ys * g.xs;
-  int32_t *d_store, *d_q, *d_sb, *d_ll; uint32_t *d_so; uint64_t total;
+  int32_t *d_store, *d_q, *d_ll; Budgets b;
   NEED(c, B_STORE, (size_t)ns * g.slice_coefs * 4, d_store);
   NEED(c, B_QIDX, (size_t)ns * 4, d_q);
   NEED(c, B_LL0, ll_bytes(g, 1) + 16, d_ll);
@@ -1790,9 +1874,9 @@ extern "C" int vc2hip_ld_qindices(vc2hip_ctx *c, const int32_t *y, const int32_t
   ll_layout(g, 1, d_ll, ll);
   const int32_t *pl[3] = {y, u, v};
   if ((rc = planes_to_store(c, g, pl, d_store))) return rc;
-  if ((rc = ld_offsets_upload(c, slice_bytes, ns, &d_sb, &d_so, &total))) return rc;
+  if ((rc = budget_tables(c, g.ys, g.xs, 0, 1, LD_BUDGETS, b, slice_bytes))) return rc;
   LdEncParams p;
-  if ((rc = fill_ld_enc(c, p, g, d_store, d_q, qm, ll, d_sb, d_so, 0, nullptr, 0))) return rc;
+  if ((rc = fill_ld_enc(c, p, g, records32(g, d_store), d_q, qm, ll, b, 0, nullptr, 0))) return rc;
   p.search = 1;
   vc2_launch_ld_quantise(c->L, p, 1, c->stream);
   HIPCHK(c, hipMemcpyAsync(qidx, d_q, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1811,19 +1895,20 @@ extern "C" int vc2hip_ld_pack(vc2hip_ctx *c, const int32_t *y, const int32_t *u,
   const int ns = g.ys * g.xs;
   int mx = 1;
   for (int i = 0; i < ns; ++i) { if (slice_bytes[i] < 1) return set_err(c, VC2HIP_EINVAL); mx = std::max(mx, slice_bytes[i]); }
-  int32_t *d_store, *d_q, *d_sb; uint32_t *d_so; uint8_t *d_pay; uint64_t total;
+  int32_t *d_store, *d_q; uint8_t *d_pay; Budgets b;
   NEED(c, B_STORE, (size_t)ns * g.slice_coefs * 4, d_store);
   NEED(c, B_QIDX, (size_t)ns * 4, d_q);
   const int32_t *pl[3] = {y, u, v};
   if ((rc = planes_to_store(c, g, pl, d_store))) return rc;
   HIPCHK(c, hipMemcpyAsync(d_q, qidx, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
-  if ((rc = ld_offsets_upload(c, slice_bytes, ns, &d_sb, &d_so, &total))) return rc;
+  if ((rc = budget_tables(c, g.ys, g.xs, 0, 1, LD_BUDGETS, b, slice_bytes))) return rc;
+  const uint64_t total = b.total;
   if (total > cap) return set_err(c, VC2HIP_ECAP);
   NEED(c, B_PAYLOAD, total + 64, d_pay);
   LLPlanes ll;
   memset(&ll, 0, sizeof ll);
   LdEncParams p;
-  if ((rc = fill_ld_enc(c, p, g, d_store, d_q, nullptr, ll, d_sb, d_so, mx, d_pay, (long long)total))) return rc;
+  if ((rc = fill_ld_enc(c, p, g, records32(g, d_store), d_q, nullptr, ll, b, mx, d_pay, (long long)total))) return rc;
   vc2_launch_ld_pack(c->L, p, 1, c->stream);
   if ((rc = vc2hip_sync(c))) return rc;
   HIPCHK(c, hipMemcpy(out, d_pay, total, hipMemcpyDeviceToHost));
@@ -1920,17 +2005,17 @@ static void view_convert(vc2hip_ctx *c, const RawView &v, bool pack) {
 }
 
 // The decoder's store for n pictures of g: the slice records, behind them the band planes of the finest levels and the
-// record heads of the deep ones (planned by dry runs of run_inverse: nothing is launched).  decode_batch_common plans the
+// record heads of the deep ones (planned by a dry run of run_inverse: nothing is launched).  decode_batch_common plans the
 // store the slice decoders fill, encode_recon_batch_dev the one the requantise kernel fills for the same inverse kernels.
+// job: the inverse transform the store is for (matrix, LL source, destination) -- its band planes, record heads and head
+// level are set here; its store is the caller's to set once it is allocated.
 struct DecoderLayout {
   BandPlanes bp;
   HeadSplit hs;
-  int head_level;    // first level that reads the record heads (1 << 30: none)
   long long sstride; // elements per picture
   unsigned tails;    // levels whose streaming kernel is the TAIL instantiation
 };
-static void plan_decoder_layout(vc2hip_ctx *c, const Geom &g, int kernel, int n, bool ld, const int32_t *qm, void *const dst[3], const RawPlane ds[3],
-                                const vc2hip_picture_format *f, bool s16, bool plane_path, DecoderLayout &lay) {
+static void plan_decoder_layout(vc2hip_ctx *c, const Geom &g, int kernel, int n, bool s16, bool plane_path, InverseJob &job, DecoderLayout &lay) {
   // Band planes (vc2hip_internal.h): the finest levels, as long as they go through the streaming inverse kernel, a
   // slice's block row in them is at least 4 coefficients (8: rows that keep 16-byte pieces aligned) and they are not
   // the level whose LL comes from the store.  16-bit store only (the int32 store is the fallback decoder's).
@@ -1938,15 +2023,18 @@ static void plan_decoder_layout(vc2hip_ctx *c, const Geom &g, int kernel, int n,
   HeadSplit &hs = lay.hs;
   memset(&lay, 0, sizeof lay);
   const int ns = g.ys * g.xs;
-  int head_level = 1 << 30;
-  long long sstride = (long long)ns * g.slice_coefs; // elements per picture: slice records, then band planes
-  if (s16 && !plane_path && c->allow_planes) {
-    unsigned mask = 0;
+  long long sstride = record_stride(g); // elements per picture: slice records, then band planes
+  InversePlan plan = {0, 0, 0};
+  if (s16 && !plane_path && (c->allow_planes || c->allow_heads)) { // which kernel each level would run on
     LLPlanes none;
     memset(&none, 0, sizeof none);
-    unsigned &tails = lay.tails;
-    (void)run_inverse(c, g, kernel, n, nullptr, nullptr, qm, true, ld, none, dst, ds, true, f, s16, nullptr, nullptr, 0, &mask, nullptr, 1 << 30,
-                      nullptr, &tails);
+    InverseJob dry = job;
+    dry.store = Store{nullptr, nullptr, s16, sstride};
+    (void)run_inverse(c, g, kernel, n, dry, none, &plan);
+  }
+  if (s16 && !plane_path && c->allow_planes) {
+    const unsigned mask = plan.stream;
+    lay.tails = plan.tail;
     for (int k = 0; k < 3; ++k) bp.from[k] = g.c[k].ph ? g.c[k].sh * g.c[k].sw : 0;
     for (int l = 0; l < VC2_BP_MAX && l < g.depth - 1 && (mask >> l & 1); ++l) {
       bool ok = true;
@@ -1970,15 +2058,12 @@ static void plan_decoder_layout(vc2hip_ctx *c, const Geom &g, int kernel, int n,
       }
       bp.levels = l + 1;
     }
-    if (sstride >= (1ll << 31)) { memset(&bp, 0, sizeof bp); sstride = (long long)ns * g.slice_coefs; } // 32-bit element offsets
+    if (sstride >= (1ll << 31)) { memset(&bp, 0, sizeof bp); sstride = record_stride(g); } // 32-bit element offsets
   }
   // Record heads (HeadSplit, vc2hip_internal.h): the levels below the streaming ones, when all of them run on the tile
   // kernels, read their coefficients from dense per-component arrays behind the records (and band planes)
   if (s16 && !plane_path && c->allow_heads) {
-    unsigned smask = 0, fmask = 0;
-    LLPlanes none;
-    memset(&none, 0, sizeof none);
-    (void)run_inverse(c, g, kernel, n, nullptr, nullptr, qm, true, ld, none, dst, ds, true, f, s16, nullptr, nullptr, 0, &smask, nullptr, 1 << 30, &fmask);
+    const unsigned smask = plan.stream, fmask = plan.fast;
     int ls = g.depth; // first level of the run of tile-kernel levels that reaches the deepest one
     while (ls > 0 && !(smask >> (ls - 1) & 1) && (fmask >> (ls - 1) & 1)) --ls;
     bool ok = ls >= 1 && ls < g.depth && ls >= bp.levels; // (level 0 keeps its bands where the final kernels expect them)
@@ -1995,10 +2080,11 @@ static void plan_decoder_layout(vc2hip_ctx *c, const Geom &g, int kernel, int n,
         hs.base[k] = at;
         at += ((long long)ns * hs.n[k] + 7) & ~7ll;
       }
-      if (at < (1ll << 31)) { sstride = at; head_level = ls; } else memset(&hs, 0, sizeof hs);
+      if (at < (1ll << 31)) { sstride = at; job.head_level = ls; } else memset(&hs, 0, sizeof hs);
     }
   }
-  lay.head_level = head_level;
+  job.bp = &bp;
+  job.hs = hs.n[0] ? &hs : nullptr;
   lay.sstride = sstride;
 }
 
@@ -2011,9 +2097,8 @@ struct ReconOut {
 static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, int fields, int top_first, int n,
                                const vc2hip_picture_format *fb, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
                                void *d_payload, size_t payload_stride, uint64_t *d_lens, const ReconOut *ro = nullptr);
-static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f, const int32_t *qm,
-                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const struct RawView &in, const ReconOut &ro,
-                     const int32_t *d_cb, bool check, const LdEncParams *ld);
+static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f,
+                     const PackJob &job, const LdEncParams &lp, const LLPlanes &ll, const struct RawView &in, const ReconOut &ro);
 
 // ---- the front of the six device batch calls -------------------------------------------------------------------------
 // Every call refuses what it can see in its arguments here, before it records the fork event or enters the context: a
@@ -2117,6 +2202,7 @@ static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, 
     NEED(c, B_LLW, ll_bytes(g, n) + 16, d_llw);
   }
   NEED(c, B_QIDX, (size_t)n * ns * 4, d_q);
+  const Store st = {d_store, d_storew, s16, record_stride(g)};
   LLPlanes ll;
   ll_layout(g, n, d_ll, s16 ? 2 : 4, d_llw, ll);
   const void *src[3]; RawPlane ss[3];
@@ -2126,88 +2212,80 @@ static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, 
   view_planes(in, fb, fields, top_first, src, ss);
   if (needs_plane_path(c, g, cp->kernel)) { // (a slice beyond any LDS tile: HQ and LD alike -- the store is int32 then)
     if ((rc = plane_forward(c, g, cp->kernel, n, src, ss, f, d_store))) return rc;
-  } else if ((rc = run_forward(c, g, cp->kernel, n, src, ss, true, f, d_store, ll, s16, d_storew))) return rc;
-  int32_t *d_cb = nullptr; uint32_t *d_co = nullptr; uint64_t total = 0;
-  if (cp->mode == VC2HIP_LD) {
-    // EncodeStream.cpp:509-512 (slice_bytes with scalar 1), :141-245, :195-244
-    const int key[5] = {g.ys, g.xs, cp->compressed_bytes, 1, -7};
-    if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
-      std::vector<int32_t> sb(ns);
-      vc2hip_slice_bytes(g.ys, g.xs, cp->compressed_bytes, 1, sb.data());
-      if ((rc = ld_offsets_upload(c, sb.data(), ns, &d_cb, &d_co, &total))) return rc;
-      memcpy(c->cbr_key, key, sizeof key);
-      c->cbr_total = total;
-    }
-    d_cb = (int32_t *)c->buf[B_CBRB].p; d_co = (uint32_t *)c->buf[B_CBRO].p; total = c->cbr_total;
-    if (d_payload && total > payload_stride) return set_err(c, VC2HIP_ECAP);
-    LdEncParams p;
+  } else if ((rc = run_forward(c, g, cp->kernel, n, src, ss, true, f, st, ll))) return rc;
+  const bool ld = cp->mode == VC2HIP_LD, cbr = cp->mode == VC2HIP_HQ_CBR;
+  Budgets b = {};
+  if (ld) rc = budget_tables(c, g.ys, g.xs, cp->compressed_bytes, 1, LD_BUDGETS, b);
+  else if (cbr) rc = budget_tables(c, g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix, b);
+  if (rc) return rc;
+  // a slot holds the budgets' sum, or whatever a slice's three length bytes can describe
+  const size_t slot_bytes = b.bytes ? (size_t)b.total : vc2hip_max_payload_bytes(f, cp);
+  if (d_payload && payload_stride < slot_bytes) return set_err(c, VC2HIP_ECAP);
+  LdEncParams lp;
+  if (ld) { // EncodeStream.cpp:141-245, :195-244
     c->ld_batch = n;
-    if ((rc = fill_ld_enc(c, p, g, d_store, d_q, qm, ll, d_cb, d_co, cp->compressed_bytes / ns + 5, (uint8_t *)d_payload,
+    if ((rc = fill_ld_enc(c, lp, g, st, d_q, qm, ll, b, cp->compressed_bytes / ns + 5, (uint8_t *)d_payload,
                           (long long)payload_stride))) return rc;
-    p.search = 1;
-    vc2_launch_ld_quantise(c->L, p, n, c->stream);
+    lp.search = 1;
+    vc2_launch_ld_quantise(c->L, lp, n, c->stream);
     if (d_payload) {
-      vc2_launch_ld_pack(c->L, p, n, c->stream);
-      vc2_launch_fill_u64(c->L, (unsigned long long *)d_lens, total, (size_t)n, c->stream);
+      vc2_launch_ld_pack(c->L, lp, n, c->stream);
+      vc2_launch_fill_u64(c->L, (unsigned long long *)d_lens, b.total, (size_t)n, c->stream);
     }
-    return ro ? run_recon(c, g, cp, n, f, qm, false, d_store, nullptr, d_q, ll, in, *ro, d_cb, !d_payload, &p) : VC2HIP_OK;
-  }
-  if (cp->mode == VC2HIP_HQ_CBR) {
-      const int key[5] = {g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix};
-    if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
-      std::vector<int32_t> sb(ns);
-      vc2hip_slice_bytes(g.ys, g.xs, cp->compressed_bytes, cp->scalar, sb.data());
-      if ((rc = cbr_offsets_upload(c, sb.data(), ns, cp->prefix, &d_cb, &d_co, &total))) return rc;
-      memcpy(c->cbr_key, key, sizeof key);
-      c->cbr_total = total;
-    }
-    d_cb = (int32_t *)c->buf[B_CBRB].p; d_co = (uint32_t *)c->buf[B_CBRO].p; total = c->cbr_total;
-    if (d_payload && total > payload_stride) return set_err(c, VC2HIP_ECAP);
+  } else if (cbr) {
     CbrParams p;
-    memset(&p, 0, sizeof p);
-    p.store = d_store; p.store_stride = (long long)ns * g.slice_coefs; p.qidx = d_q; p.slice_bytes = d_cb;
-    p.store16 = s16; p.store_wide = d_storew;
-    p.n_slices = ns; p.slice_coefs = g.slice_coefs;
-    fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
-    p.scalar = cp->scalar; p.err = c->d_err;
-    p.general_only = c->cbr_general;
-    for (int b = 0; b < 3 * g.depth + 1; ++b) p.qmatrix[b] = qm[b];
-    p.n_bands = 3 * g.depth + 1;
+    fill_cbr(p, g, st, d_q, b.bytes, cp->scalar, qm, c->cbr_general, c->d_err);
     vc2_launch_cbr(c->L, p, n, c->stream);
   } else if (cp->mode == VC2HIP_HQ_CAPPED) { // one index per picture, found on the device (vc2hip_cap.h)
-    if (d_payload && payload_stride < vc2hip_max_payload_bytes(f, cp)) return set_err(c, VC2HIP_ECAP);
     CapParams p;
     memset(&p, 0, sizeof p);
     NEED(c, B_CAPTAB, (size_t)n * VC2_CAP_ROW * 8, p.table);
     HIPCHK(c, hipMemsetAsync(p.table, 0, (size_t)n * VC2_CAP_ROW * 8, c->stream));
-    p.s.store = d_store; p.s.store_stride = (long long)ns * g.slice_coefs; p.s.qidx = d_q;
-    p.s.store16 = s16; p.s.store_wide = d_storew;
-    p.s.n_slices = ns; p.s.slice_coefs = g.slice_coefs;
-    fill_comp_arrays(g, p.s.comp_n, p.s.comp_off, p.s.comp_n0);
-    p.s.scalar = cp->scalar; p.s.err = c->d_err;
-    p.s.general_only = c->cap_general;
-    for (int b = 0; b < 3 * g.depth + 1; ++b) p.s.qmatrix[b] = qm[b];
-    p.s.n_bands = 3 * g.depth + 1;
+    fill_cbr(p.s, g, st, d_q, b.bytes, cp->scalar, qm, c->cap_general, c->d_err); // (no budgets: the cap is the picture's)
     p.prefix = cp->prefix; p.floor = cp->q_index; p.cap = (unsigned long long)cp->compressed_bytes;
     vc2_launch_cap(c->L, p, n, c->stream);
   } else {
-    if (d_payload && payload_stride < vc2hip_max_payload_bytes(f, cp)) return set_err(c, VC2HIP_ECAP);
     // quantIndicesConstQ, EncodeStream.cpp:128-138
     vc2_launch_fill_i32(c->L, d_q, cp->q_index, (size_t)n * ns, c->stream);
   }
-  if (d_payload && (rc = run_pack(c, g, n, d_store, d_q, qm, true, cp->prefix, cp->scalar, d_cb, d_co, total, (uint8_t *)d_payload,
-                                  (long long)payload_stride, (unsigned long long *)d_lens, s16, d_storew))) return rc;
-  return ro ? run_recon(c, g, cp, n, f, qm, s16, d_store, d_storew, d_q, ll, in, *ro, d_cb, !d_payload, nullptr) : VC2HIP_OK;
+  PackJob job; // what the coder is handed: run_pack codes it (LD's slices are written above), run_recon decodes it
+  job.store = st; job.qidx = d_q; job.qm = qm;
+  job.prefix = cp->prefix; job.scalar = cp->scalar; job.budgets = b;
+  job.payload = (uint8_t *)d_payload; job.stride = (long long)payload_stride; job.lens = (unsigned long long *)d_lens;
+  if (d_payload && !ld && (rc = run_pack(c, g, n, job))) return rc;
+  return ro ? run_recon(c, g, cp, n, f, job, lp, ll, in, *ro) : VC2HIP_OK;
+}
+
+// A squared-error job over the pictures of a and b, which lie in one layout: the sample words here, the components by sse_comp
+static void sse_job(SseParams &p, const vc2hip_picture_format *f, int le, int lsb, const void *a, const void *b, size_t pic_bytes, uint64_t *sse) {
+  memset(&p, 0, sizeof p);
+  p.a = (const uint8_t *)a; p.b = (const uint8_t *)b; p.pic_bytes = (long long)pic_bytes;
+  p.word_bytes = f->word_bytes; p.shift = lsb ? 0 : 8 * f->word_bytes - f->bit_depth;
+  p.mask = f->bit_depth < 32 ? (1u << f->bit_depth) - 1 : ~0u;
+  p.le = le;
+  p.sse = (unsigned long long *)sse;
+}
+// component k of the job: its first row `at` bytes into a picture, its rows `pitch` bytes apart
+static void sse_comp(SseParams &p, int k, const CompGeom &cg, size_t at, size_t pitch) {
+  const long long row = (long long)cg.w * p.word_bytes;
+  const bool tight = (long long)pitch == row; // one run of bytes: the kernel's "one row"
+  p.comp_at[k] = (long long)at;
+  p.rows[k] = tight ? 1 : cg.h;
+  p.row_bytes[k] = tight ? row * cg.h : row;
+  p.pitch[k] = (long long)pitch;
 }
 
 // What follows the slice coder in vc2hip_encode_recon_batch_dev: the indices, the decoder's picture from the quantised
 // coefficients (no payload is read: DESIGN.md section 12), the squared error.  HQ: d_store holds transform coefficients,
 // which k_requantise turns into the decoder's store; LD: vc2_launch_ld_quantise left quantised values with LL residuals in
-// it, which is what the decoder's slice reader leaves.  check: no payload was written, the coder's checks are made here.
-static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f, const int32_t *qm,
-                     bool s16, int32_t *d_store, int32_t *d_storew, int32_t *d_q, const LLPlanes &ll, const RawView &in, const ReconOut &ro,
-                     const int32_t *d_cb, bool check, const LdEncParams *ld) {
+// it, which is what the decoder's slice reader leaves.  job: the slice coder's, with no payload where none was written --
+// the coder's checks are made here then; lp: LD's search job (set for LD pictures only).
+static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f,
+                     const PackJob &job, const LdEncParams &lp, const LLPlanes &ll, const RawView &in, const ReconOut &ro) {
   const int ns = g.ys * g.xs;
+  const Store &st = job.store;
+  const int32_t *const qm = job.qm, *const d_q = job.qidx;
+  const bool s16 = st.s16, ld = cp->mode == VC2HIP_LD, check = !job.payload;
   int rc;
   if (ro.qidx) HIPCHK(c, hipMemcpyAsync(ro.qidx, d_q, (size_t)n * ns * 4, hipMemcpyDeviceToDevice, c->stream));
   const void *dstc[3]; RawPlane ds[3];
@@ -2216,30 +2294,18 @@ static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *c
   view_planes(out, f, 1, 1, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
+  InverseJob inv; // the decoder's inverse transform of the store the branches below leave
+  inv.qidx = d_q; inv.qm = qm;
+  inv.dst = dst; inv.dst_l = ds; inv.f = f;
+  DecoderLayout lay; // (HQ)
   if (ld) {
-    if (check) vc2_launch_ld_check(c->L, *ld, n, c->stream);
-    if (ro.recon) {
-      LdLl3Params lp;
-      lp.store = d_store; lp.store_stride = (long long)ns * g.slice_coefs; lp.slice_coefs = g.slice_coefs;
-      lp.ys = g.ys; lp.xs = g.xs; lp.qidx = d_q; lp.qm0 = qm[0]; lp.err = c->d_err;
-      for (int k = 0; k < 3; ++k) {
-        lp.coef_off[k] = g.c[k].coef_off; lp.llh[k] = g.c[k].ph >> g.depth; lp.llw[k] = g.c[k].pw >> g.depth;
-        lp.ll_plane[k] = (int32_t *)ll.p[g.depth][k]; lp.ll_stride[k] = ll.stride[g.depth][k];
-      }
-      if (!vc2_launch_ld_ll3(c->L, lp, n, c->stream))
-        for (int k = 0; k < 3; ++k)
-          vc2_launch_ld_ll(c->L, d_store, (long long)ns * g.slice_coefs, g.slice_coefs, g.c[k].coef_off, g.c[k].n0,
-                           g.c[k].ph >> g.depth, g.c[k].pw >> g.depth, g.ys, g.xs, d_q, qm[0], (int32_t *)ll.p[g.depth][k],
-                           ll.stride[g.depth][k], n, c->d_err, c->stream);
-      if (plane_path) rc = plane_inverse(c, g, cp->kernel, n, d_store, d_q, qm, dst, ds, f, &ll);
-      else rc = run_inverse(c, g, cp->kernel, n, d_store, d_q, qm, true, true, ll, dst, ds, true, f);
-      if (rc) return rc;
-    }
+    if (check) vc2_launch_ld_check(c->L, lp, n, c->stream);
+    if (ro.recon) ld_restore_ll(c, g, n, st, d_q, qm[0], ll);
+    inv.store = st; inv.ll_ready = true;
   } else if (ro.recon || check) {
     // the decoder's layout, as decode_batch_common plans it for the same pictures (16-bit band planes: the byte form
     // follows the statistics of a context's previous decode batch, which this call neither reads nor changes)
-    DecoderLayout lay;
-    plan_decoder_layout(c, g, cp->kernel, n, false, qm, dst, ds, f, s16, plane_path, lay);
+    plan_decoder_layout(c, g, cp->kernel, n, s16, plane_path, inv, lay);
     int32_t *d_rs = nullptr, *d_rsw = nullptr;
     if (ro.recon) {
       NEED(c, B_RSTORE, (size_t)n * (size_t)lay.sstride * (s16 ? 2 : 4), d_rs);
@@ -2247,98 +2313,105 @@ static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *c
     }
     RequantParams p;
     memset(&p, 0, sizeof p);
-    p.src = d_store; p.src_wide = d_storew; p.src_stride = (long long)ns * g.slice_coefs;
+    p.src = st.p; p.src_wide = st.wide; p.src_stride = st.stride;
     p.dst = d_rs; p.dst_wide = d_rsw; p.dst_stride = lay.sstride;
     p.store16 = s16; p.qidx = d_q; p.n_slices = ns; p.slice_coefs = g.slice_coefs; p.xs = g.xs;
     fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
     p.n_bands = 3 * g.depth + 1;
-    for (int b = 0; b < p.n_bands; ++b) p.qmatrix[b] = qm[b];
+    for (int i = 0; i < p.n_bands; ++i) p.qmatrix[i] = qm[i];
     p.bp = lay.bp; p.hs = lay.hs;
-    p.check = check; p.scalar = cp->scalar; p.cbr_bytes = d_cb; p.err = c->d_err;
+    p.check = check; p.scalar = cp->scalar; p.cbr_bytes = job.budgets.bytes; p.err = c->d_err;
     vc2_launch_requantise(c->L, p, n, c->stream);
-    if (ro.recon) {
-      if (plane_path) rc = plane_inverse(c, g, cp->kernel, n, d_rs, d_q, qm, dst, ds, f);
-      else rc = run_inverse(c, g, cp->kernel, n, d_rs, d_q, qm, true, false, ll, dst, ds, true, f, s16, d_rsw, &lay.bp, lay.sstride, nullptr,
-                            lay.hs.n[0] ? &lay.hs : nullptr, lay.head_level);
-      if (rc) return rc;
-    }
+    inv.store = Store{d_rs, d_rsw, s16, lay.sstride};
   }
-  if (ro.recon) view_convert(c, out, true);
-  if (ro.sse && out.packed) { // the two stagings (semi-planar: the Y planes where they are, in a launch of their own)
-    HIPCHK(c, hipMemsetAsync(ro.sse, 0, (size_t)n * 3 * 8, c->stream));
-    vc2_prof_break(c->L);
+  if (ro.recon) {
+    if (plane_path) rc = plane_inverse(c, g, cp->kernel, n, (const int32_t *)inv.store.p, d_q, qm, dst, ds, f, ld ? &ll : nullptr);
+    else rc = run_inverse(c, g, cp->kernel, n, inv, ll);
+    if (rc) return rc;
+    view_convert(c, out, true);
+  }
+  if (!ro.sse) return VC2HIP_OK;
+  HIPCHK(c, hipMemsetAsync(ro.sse, 0, (size_t)n * 3 * 8, c->stream));
+  vc2_prof_break(c->L);
+  SseParams p;
+  if (out.packed) { // the two stagings (semi-planar: the Y planes where they are, in a launch of their own)
     const bool v210 = out.pl.packing == VC2HIP_PACKING_V210;
-    SseParams p;
-    memset(&p, 0, sizeof p);
-    p.word_bytes = f->word_bytes; p.shift = v210 || out.pl.lsb ? 0 : 8 * f->word_bytes - f->bit_depth;
-    p.mask = f->bit_depth < 32 ? (1u << f->bit_depth) - 1 : ~0u;
-    p.le = v210 ? 1 : out.pl.le;
-    p.sse = (unsigned long long *)ro.sse;
-    SseParams ps = p; // the staged components
-    ps.a = in.stage; ps.b = out.stage; ps.pic_bytes = (long long)out.sstride;
-    for (int k = v210 ? 0 : 1; k < 3; ++k) {
-      const long long row = (long long)g.c[k].w * f->word_bytes;
-      const bool tight = (long long)out.spitch[k] == row;
-      ps.comp_at[k] = (long long)out.sat[k];
-      ps.rows[k] = tight ? 1 : g.c[k].h;
-      ps.row_bytes[k] = tight ? row * g.c[k].h : row;
-      ps.pitch[k] = (long long)out.spitch[k];
-    }
-    vc2_launch_squared_error(c->L, ps, n, c->stream);
-    if (!v210) {
-      p.a = (const uint8_t *)in.base; p.b = (const uint8_t *)out.base; p.pic_bytes = (long long)out.pl.stride;
-      const long long row = (long long)g.c[0].w * f->word_bytes;
-      const bool tight = (long long)out.pl.pitch[0] == row;
-      p.comp_at[0] = (long long)out.pl.at[0];
-      p.rows[0] = tight ? 1 : g.c[0].h;
-      p.row_bytes[0] = tight ? row * g.c[0].h : row;
-      p.pitch[0] = (long long)out.pl.pitch[0];
-      vc2_launch_squared_error(c->L, p, n, c->stream);
-    }
-  } else if (ro.sse) {
-    HIPCHK(c, hipMemsetAsync(ro.sse, 0, (size_t)n * 3 * 8, c->stream));
-    vc2_prof_break(c->L);
-    SseParams p;
-    memset(&p, 0, sizeof p);
-    p.a = (const uint8_t *)in.base; p.b = (const uint8_t *)ro.recon;
-    RawLayout lay;
-    (void)resolve_layout(f, active_layout(c), lay); // (refused at the entry point)
-    p.pic_bytes = (long long)lay.stride;
-    for (int k = 0; k < 3; ++k) {
-      const long long row = (long long)g.c[k].w * f->word_bytes;
-      const bool tight = (long long)lay.pitch[k] == row; // one run of bytes: the kernel's "one row"
-      p.comp_at[k] = (long long)lay.at[k];
-      p.rows[k] = tight ? 1 : g.c[k].h;
-      p.row_bytes[k] = tight ? row * g.c[k].h : row;
-      p.pitch[k] = (long long)lay.pitch[k];
-    }
-    p.word_bytes = f->word_bytes; p.shift = lay.lsb ? 0 : 8 * f->word_bytes - f->bit_depth;
-    p.mask = f->bit_depth < 32 ? (1u << f->bit_depth) - 1 : ~0u;
-    p.le = lay.le;
-    p.sse = (unsigned long long *)ro.sse;
+    const int le = v210 ? 1 : out.pl.le, lsb = v210 ? 1 : out.pl.lsb;
+    sse_job(p, f, le, lsb, in.stage, out.stage, out.sstride, ro.sse);
+    for (int k = v210 ? 0 : 1; k < 3; ++k) sse_comp(p, k, g.c[k], out.sat[k], out.spitch[k]);
     vc2_launch_squared_error(c->L, p, n, c->stream);
+    if (v210) return VC2HIP_OK;
+    sse_job(p, f, le, lsb, in.base, out.base, out.pl.stride, ro.sse);
+    sse_comp(p, 0, g.c[0], out.pl.at[0], out.pl.pitch[0]);
+  } else {
+    RawLayout rl;
+    (void)resolve_layout(f, active_layout(c), rl); // (refused at the entry point)
+    sse_job(p, f, rl.le, rl.lsb, in.base, ro.recon, rl.stride, ro.sse);
+    for (int k = 0; k < 3; ++k) sse_comp(p, k, g.c[k], rl.at[k], rl.pitch[k]);
   }
+  vc2_launch_squared_error(c->L, p, n, c->stream);
   return VC2HIP_OK;
 }
 
 // HQ_CBR pictures on the decoding side: the caller says CBR, so the budgets predict the slice offsets (the claim that
-// vc2_launch_cbr_index verifies).  The budget tables of cp, uploaded when they are not the ones the context holds; all
-// three stay null / 0 where cp is not HQ_CBR or the context never claims (VC2HIP_FLAG_NO_CBR_INDEX).
-static void cbr_claim_tables(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, const int32_t **d_cb, const uint32_t **d_co,
-                             uint64_t *cbr_total) {
-  if (!(cp->mode == VC2HIP_HQ_CBR && cp->compressed_bytes > 0 && c->allow_cbr_index)) return;
-  const int ns = g.ys * g.xs;
-  const int key[5] = {g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix};
-  if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
-    std::vector<int32_t> sb(ns);
-    int32_t *db; uint32_t *dof; uint64_t total;
-    if (vc2hip_slice_bytes(g.ys, g.xs, cp->compressed_bytes, cp->scalar, sb.data()) == VC2HIP_OK &&
-        cbr_offsets_upload(c, sb.data(), ns, cp->prefix, &db, &dof, &total) == VC2HIP_OK) {
-      memcpy(c->cbr_key, key, sizeof key);
-      c->cbr_total = total;
-    }
+// vc2_launch_cbr_index verifies).  The budget tables of cp; none where cp is not HQ_CBR, the context never claims
+// (VC2HIP_FLAG_NO_CBR_INDEX) or the tables could not be made: the general index then works alone.
+static Budgets cbr_claim_tables(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp) {
+  Budgets b = {};
+  if (cp->mode == VC2HIP_HQ_CBR && cp->compressed_bytes > 0 && c->allow_cbr_index)
+    (void)budget_tables(c, g.ys, g.xs, cp->compressed_bytes, cp->scalar, cp->prefix, b); // (a failure leaves b empty)
+  return b;
+}
+
+// One byte per band-plane coefficient for this batch?  What the previous batch of this context looked like decides (its
+// lengths and its escape count arrive through pinned memory behind an event: no wait here): small coefficients <=> few
+// payload bits per sample.  The planes keep their places and their wide elements: only the bytes of a plane's narrow
+// elements halve.  levels, tails: of the batch's band planes (DecoderLayout).
+static bool choose_bytes8(vc2hip_ctx *c, bool capturing, int levels, unsigned tails) {
+  // (the context's FIRST look is waited for -- once, at its second batch, while the first is all the GPU has to do
+  // anyway: a caller that never synchronises between batches would otherwise keep the 16-bit planes for as long as it
+  // runs ahead of the GPU; every later look is only taken when it has arrived.  Never on a caller's stream
+  // (vc2hip_create_on_stream): that caller may be capturing a graph or deliberately running ahead of the GPU -- there
+  // the look is only ever queried, and VC2HIP_FLAG_PLANES8_ALWAYS / _NEVER make the choice deterministic: include/vc2hip.h.
+  // The lanes of such a context follow the same rule.  During a capture the look is not even queried: the form a
+  // captured call is planned with is the one the context had when the capture began)
+  if (c->stat_pending && !c->stat_seen && !c->follows_caller) (void)hipEventSynchronize(c->stat_ev);
+  if (c->stat_pending && !capturing && hipEventQuery(c->stat_ev) == hipSuccess) {
+    c->stat_pending = false;
+    c->stat_seen = true;
+    double bytes = 0;
+    for (int k = 0; k < c->stat_n; ++k) bytes += (double)c->h_stat[1 + k];
+    const double bits = c->stat_n ? 8.0 * bytes / (c->stat_n * c->stat_samples) : 99.0;
+    // (pieces of eight coefficients; counted over ALL pictures of the batch, not only the stat_n whose lengths were copied)
+    const double esc = (double)c->h_stat[0] * 8.0 / (std::max(1, c->stat_n_total) * c->stat_samples);
+#ifdef VC2HIP_ABLATE
+    if (getenv("VC2HIP_PLANES8_DEBUG")) fprintf(stderr, "planes8: previous batch %d pictures, %.2f payload bits per sample, %s planes, escape pieces %.4f%%\n", c->stat_n, bits, c->stat_was8 ? "byte" : "16-bit", 100 * esc);
+#endif
+    if (c->stat_was8 && esc > 0.005) c->planes8_on = false;       // more than 0.5 % of the pieces carried an escape
+    else if (!c->stat_was8 || esc < 0.002) c->planes8_on = bits < (c->planes8_on ? 6.5 : 6.0);
   }
-  if (!memcmp(key, c->cbr_key, sizeof key)) { *d_cb = (const int32_t *)c->buf[B_CBRB].p; *d_co = (const uint32_t *)c->buf[B_CBRO].p; *cbr_total = c->cbr_total; }
+  bool b8 = c->planes8_mode == 1 || (c->planes8_mode == 0 && c->planes8_on);
+  for (int l = 0; l < levels; ++l) if (tails >> l & 1) b8 = false; // (the TAIL instantiations read 16-bit planes only)
+  return b8;
+}
+// The HQ slice reader's launch, and where the next call's choice is open this batch's escape count and payload lengths for
+// it.  samples: of one coded picture
+static int unpack_and_look(vc2hip_ctx *c, const UnpackParams &p, int n, bool capturing, double samples) {
+  // (no look while the stream is being captured into a graph: the copies and the event would become graph nodes and the
+  // event could never be queried)
+  const bool look = p.bp.levels && c->planes8_mode == 0 && !c->stat_pending && !capturing;
+  if (look) HIPCHK(c, hipMemsetAsync(c->d_stat, 0, 8, c->stream));
+  vc2_launch_unpack(c->L, p, n, c->stream);
+  if (!look) return VC2HIP_OK;
+  c->stat_n = std::min(n, 60);
+  c->stat_n_total = n;
+  c->stat_samples = samples;
+  c->stat_was8 = p.bp.bytes8 != 0;
+  HIPCHK(c, hipMemcpyAsync(c->h_stat, c->d_stat, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_stat + 1, p.lens, (size_t)c->stat_n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(c->stat_ev, c->stream));
+  c->stat_pending = true;
+  return VC2HIP_OK;
 }
 
 // n coded pictures in payload slots -> the pictures of d_raw_out, whose format is fb: the coded pictures (fields 1), the
@@ -2368,13 +2441,14 @@ static int decode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_paylo
   view_planes(out, fb, fields, top_first, dstc, ds);
   void *dst[3] = {(void *)dstc[0], (void *)dstc[1], (void *)dstc[2]};
   const bool plane_path = needs_plane_path(c, g, cp->kernel);
+  InverseJob inv; // (its store and indices follow their allocation)
+  inv.qm = qm; inv.ll_ready = ld;
+  inv.norm_shift = norm_shift; inv.level_base = drop;
+  inv.dst = dst; inv.dst_l = ds; inv.f = f;
   DecoderLayout lay;
-  plan_decoder_layout(c, g, cp->kernel, n, ld, qm, dst, ds, f, s16, plane_path, lay);
+  plan_decoder_layout(c, g, cp->kernel, n, s16, plane_path, inv, lay);
   BandPlanes &bp = lay.bp;
-  HeadSplit &hs = lay.hs;
-  const int head_level = lay.head_level;
   long long sstride = lay.sstride;
-  const unsigned tails = lay.tails;
   // Is the stream being captured into a graph?  Asked of every context a caller's stream can pull into its capture: one
   // made on that stream, and the lanes of one (their own streams join the capture at the fork event).
   bool capturing = false;
@@ -2382,38 +2456,7 @@ static int decode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_paylo
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     capturing = hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
   }
-  {
-    // One byte per plane coefficient?  What the previous batch of this context looked like decides (its lengths and its
-    // escape count arrive through pinned memory behind an event: no wait here): small coefficients <=> few payload bits per
-    // sample.  The planes keep their places and their wide elements: only the bytes of a plane's narrow elements halve.
-    if (bp.levels) {
-      // (the context's FIRST look is waited for -- once, at its second batch, while the first is all the GPU has to do
-      // anyway: a caller that never synchronises between batches would otherwise keep the 16-bit planes for as long as it
-      // runs ahead of the GPU; every later look is only taken when it has arrived.  Never on a caller's stream
-      // (vc2hip_create_on_stream): that caller may be capturing a graph or deliberately running ahead of the GPU -- there
-      // the look is only ever queried, and VC2HIP_FLAG_PLANES8_ALWAYS / _NEVER make the choice deterministic: include/vc2hip.h.
-      // The lanes of such a context follow the same rule.  During a capture the look is not even queried: the form a
-      // captured call is planned with is the one the context had when the capture began)
-      if (c->stat_pending && !c->stat_seen && !c->follows_caller) (void)hipEventSynchronize(c->stat_ev);
-      if (c->stat_pending && !capturing && hipEventQuery(c->stat_ev) == hipSuccess) {
-        c->stat_pending = false;
-        c->stat_seen = true;
-        double bytes = 0;
-        for (int k = 0; k < c->stat_n; ++k) bytes += (double)c->h_stat[1 + k];
-        const double bits = c->stat_n ? 8.0 * bytes / (c->stat_n * c->stat_samples) : 99.0;
-        // (pieces of eight coefficients; counted over ALL pictures of the batch, not only the stat_n whose lengths were copied)
-        const double esc = (double)c->h_stat[0] * 8.0 / (std::max(1, c->stat_n_total) * c->stat_samples);
-#ifdef VC2HIP_ABLATE
-        if (getenv("VC2HIP_PLANES8_DEBUG")) fprintf(stderr, "planes8: previous batch %d pictures, %.2f payload bits per sample, %s planes, escape pieces %.4f%%\n", c->stat_n, bits, c->stat_was8 ? "byte" : "16-bit", 100 * esc);
-#endif
-        if (c->stat_was8 && esc > 0.005) c->planes8_on = false;       // more than 0.5 % of the pieces carried an escape
-        else if (!c->stat_was8 || esc < 0.002) c->planes8_on = bits < (c->planes8_on ? 6.5 : 6.0);
-      }
-      bool b8 = c->planes8_mode == 1 || (c->planes8_mode == 0 && c->planes8_on);
-      for (int l = 0; l < bp.levels; ++l) if (tails >> l & 1) b8 = false; // (the TAIL instantiations read 16-bit planes only)
-      bp.bytes8 = b8;
-    }
-  }
+  if (bp.levels) bp.bytes8 = choose_bytes8(c, capturing, bp.levels, lay.tails);
   int32_t *d_store, *d_ll, *d_q, *d_storew = nullptr, *d_llw = nullptr;
   {
     static const int pad = vc2_tune_int("VC2HIP_DEC_STORE_PAD", 0); // (experiment: elements between the pictures' stores; a multiple of 8)
@@ -2426,58 +2469,28 @@ static int decode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_paylo
     NEED(c, B_LLW, ll_bytes(g, n) + 16, d_llw);
   }
   NEED(c, B_QIDX, (size_t)n * ns * 4, d_q);
+  const Store st = {d_store, d_storew, s16, sstride};
   LLPlanes ll;
   ll_layout(g, n, d_ll, s16 ? 2 : 4, d_llw, ll);
   if (!ld) {
     uint32_t *d_offs;
-    const int32_t *d_cb = nullptr; const uint32_t *d_co = nullptr; uint64_t cbr_total = 0;
-    cbr_claim_tables(c, g, cp, &d_cb, &d_co, &cbr_total);
     if ((rc = build_index(c, (const uint8_t *)d_payload, (long long)payload_stride, (const unsigned long long *)d_lens, n, ns,
-                          cp->prefix, cp->scalar, &d_offs, d_cb, d_co, cbr_total))) return rc;
+                          cp->prefix, cp->scalar, &d_offs, cbr_claim_tables(c, g, cp)))) return rc;
     UnpackParams p;
-    memset(&p, 0, sizeof p);
-    p.payload = (const uint8_t *)d_payload; p.payload_stride = (long long)payload_stride;
-    p.lens = (const unsigned long long *)d_lens; p.offsets = d_offs;
-    p.store = d_store; p.store_stride = sstride; p.qidx = d_q;
-    p.store16 = s16; p.store_wide = d_storew;
-    p.n_slices = ns; p.slice_coefs = g.slice_coefs;
-    int n0[3];
-    fill_comp_arrays(g, p.comp_n, p.comp_off, n0);
-    p.prefix = cp->prefix; p.scalar = cp->scalar; p.err = c->d_err;
-    p.bp = bp; p.hs = hs; p.xs = g.xs;
+    fill_unpack(p, g, (const uint8_t *)d_payload, (long long)payload_stride, (const unsigned long long *)d_lens, d_offs, st, d_q,
+                cp->prefix, cp->scalar, c->d_err);
+    p.bp = bp; p.hs = lay.hs; p.xs = g.xs;
     c->last_plane_bits = bp.levels ? (bp.bytes8 ? 8 : 16) : 0;
     p.stats = c->d_stat;
-    // (no look while the stream is being captured into a graph: the copies and the event would become graph nodes and the
-    // event could never be queried)
-    const bool track = bp.levels && c->planes8_mode == 0 && !c->stat_pending && !capturing;
-    if (track) HIPCHK(c, hipMemsetAsync(c->d_stat, 0, 8, c->stream));
-    vc2_launch_unpack(c->L, p, n, c->stream);
-    if (track) { // this batch's escape count and payload lengths for the next call's choice
-      c->stat_n = std::min(n, 60);
-      c->stat_n_total = n;
-      c->stat_samples = 0;
-      for (int k = 0; k < 3; ++k) c->stat_samples += (double)g.c[k].h * g.c[k].w * (1 << (2 * drop)); // (the payload is the coded picture's)
-      c->stat_was8 = bp.bytes8 != 0;
-      HIPCHK(c, hipMemcpyAsync(c->h_stat, c->d_stat, 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->h_stat + 1, d_lens, (size_t)c->stat_n * 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipEventRecord(c->stat_ev, c->stream));
-      c->stat_pending = true;
-    }
+    double samples = 0;
+    for (int k = 0; k < 3; ++k) samples += (double)g.c[k].h * g.c[k].w * (1 << (2 * drop)); // (the payload is the coded picture's)
+    if ((rc = unpack_and_look(c, p, n, capturing, samples))) return rc;
   } else {
-    // DecodeStream.cpp:312, :331-333: per-slice sizes from the picture byte budget
-    int32_t *d_sb; uint32_t *d_so; uint64_t total;
-    const int key[5] = {g.ys, g.xs, cp->compressed_bytes, 1, -7};
-    if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
-      std::vector<int32_t> sb(ns);
-      vc2hip_slice_bytes(g.ys, g.xs, cp->compressed_bytes, 1, sb.data());
-      if ((rc = ld_offsets_upload(c, sb.data(), ns, &d_sb, &d_so, &total))) return rc;
-      memcpy(c->cbr_key, key, sizeof key);
-      c->cbr_total = total;
-    }
-    d_sb = (int32_t *)c->buf[B_CBRB].p; d_so = (uint32_t *)c->buf[B_CBRO].p; total = c->cbr_total;
-    if (total > payload_stride) return set_err(c, VC2HIP_ESTREAM);
+    Budgets b;
+    if ((rc = budget_tables(c, g.ys, g.xs, cp->compressed_bytes, 1, LD_BUDGETS, b))) return rc;
+    if (b.total > payload_stride) return set_err(c, VC2HIP_ESTREAM);
     LdUnpackParams p;
-    fill_ld_unpack(p, g, (const uint8_t *)d_payload, (long long)payload_stride, d_sb, d_so, d_store, d_q, c->d_err);
+    fill_ld_unpack(p, g, (const uint8_t *)d_payload, (long long)payload_stride, b, st, d_q, c->d_err);
     // slices whose luma length exceeds the slice (corrupt pictures): flag, serial walk, second pass (LdUnpackParams)
     unsigned *d_shifted; uint32_t *d_starts;
     NEED(c, B_SIZES, (size_t)n * 4, d_shifted);
@@ -2493,22 +2506,11 @@ static int decode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_paylo
     vc2_launch_ld_walk(c->L, p, n, c->stream);
     p.redo = 1;
     vc2_launch_ld_unpack(c->L, p, n, c->stream);
-    LdLl3Params lp;
-    lp.store = d_store; lp.store_stride = (long long)ns * g.slice_coefs; lp.slice_coefs = g.slice_coefs;
-    lp.ys = g.ys; lp.xs = g.xs; lp.qidx = d_q; lp.qm0 = qm[0]; lp.err = c->d_err;
-    for (int k = 0; k < 3; ++k) {
-      lp.coef_off[k] = g.c[k].coef_off; lp.llh[k] = g.c[k].ph >> g.depth; lp.llw[k] = g.c[k].pw >> g.depth;
-      lp.ll_plane[k] = (int32_t *)ll.p[g.depth][k]; lp.ll_stride[k] = ll.stride[g.depth][k];
-    }
-    if (!vc2_launch_ld_ll3(c->L, lp, n, c->stream))
-    for (int k = 0; k < 3; ++k)
-      vc2_launch_ld_ll(c->L, d_store, (long long)ns * g.slice_coefs, g.slice_coefs, g.c[k].coef_off, g.c[k].n0,
-                       g.c[k].ph >> g.depth, g.c[k].pw >> g.depth, g.ys, g.xs, d_q, qm[0], (int32_t *)ll.p[g.depth][k],
-                       ll.stride[g.depth][k], n, c->d_err, c->stream);
+    ld_restore_ll(c, g, n, st, d_q, qm[0], ll);
   }
+  inv.store = st; inv.qidx = d_q;
   if (plane_path) rc = plane_inverse(c, g, cp->kernel, n, d_store, d_q, qm, dst, ds, f, ld ? &ll : nullptr, norm_shift, drop);
-  else rc = run_inverse(c, g, cp->kernel, n, d_store, d_q, qm, true, ld, ll, dst, ds, true, f, s16, d_storew, &bp, sstride, nullptr,
-                        hs.n[0] ? &hs : nullptr, head_level, nullptr, nullptr, norm_shift, drop);
+  else rc = run_inverse(c, g, cp->kernel, n, inv, ll);
   if (!rc) view_convert(c, out, true);
   return rc;
 }
@@ -2629,16 +2631,9 @@ extern "C" int vc2hip_stream_write_fragments_dev(vc2hip_ctx *c, const void *d_pa
                           cp->prefix, cp->scalar, &d_offs))) return rc;
     p.offs = d_offs; p.offs_stride = ns;
   } else { // the per-slice budget table the LD coder uses (vc2hip_encode_batch_dev / decode_batch_dev)
-    const int key[5] = {cp->y_slices, cp->x_slices, cp->compressed_bytes, 1, -7};
-    if (memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
-      std::vector<int32_t> sb(ns);
-      int32_t *d_sb; uint32_t *d_so; uint64_t total;
-      vc2hip_slice_bytes(cp->y_slices, cp->x_slices, cp->compressed_bytes, 1, sb.data());
-      if ((rc = ld_offsets_upload(c, sb.data(), ns, &d_sb, &d_so, &total))) return rc;
-      memcpy(c->cbr_key, key, sizeof key);
-      c->cbr_total = total;
-    }
-    p.offs = (const uint32_t *)c->buf[B_CBRO].p; p.offs_stride = 0; p.ld_total = c->cbr_total;
+    Budgets b;
+    if ((rc = budget_tables(c, cp->y_slices, cp->x_slices, cp->compressed_bytes, 1, LD_BUDGETS, b))) return rc;
+    p.offs = b.offs; p.offs_stride = 0; p.ld_total = b.total;
   }
   NEED(c, B_FRAGS, (size_t)n * ns * sizeof(uint4), p.table);
   char *pic;
@@ -2740,20 +2735,14 @@ static int transcode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_in
   NEED(c, B_TCLEN, (size_t)n * ns * 4, p.qpack);
   NEED(c, B_TCQ, (size_t)n * 4, p.qpic);
   if (tp->cap_bytes > 0) NEED(c, B_CAPTAB, (size_t)n * VC2_CAP_ROW * 8, p.table);
+  const Store st = {d_store, d_storew, s16, sstride};
   uint32_t *d_offs;
-  const int32_t *d_cb = nullptr; const uint32_t *d_co = nullptr; uint64_t cbr_total = 0;
-  cbr_claim_tables(c, g, cp, &d_cb, &d_co, &cbr_total);
   if ((rc = build_index(c, (const uint8_t *)d_in, (long long)stride_in, (const unsigned long long *)d_lens_in, n, ns, cp->prefix,
-                        cp->scalar, &d_offs, d_cb, d_co, cbr_total))) return rc;
+                        cp->scalar, &d_offs, cbr_claim_tables(c, g, cp)))) return rc;
   UnpackParams u;
-  memset(&u, 0, sizeof u);
-  u.payload = (const uint8_t *)d_in; u.payload_stride = (long long)stride_in; u.lens = (const unsigned long long *)d_lens_in; u.offsets = d_offs;
-  u.store = d_store; u.store_stride = sstride; u.qidx = d_q;
-  u.store16 = s16; u.store_wide = d_storew;
-  u.n_slices = ns; u.slice_coefs = g.slice_coefs;
-  int n0[3];
-  fill_comp_arrays(g, u.comp_n, u.comp_off, n0);
-  u.prefix = cp->prefix; u.scalar = cp->scalar; u.err = c->d_err; u.xs = g.xs; u.stats = c->d_stat;
+  fill_unpack(u, g, (const uint8_t *)d_in, (long long)stride_in, (const unsigned long long *)d_lens_in, d_offs, st, d_q, cp->prefix,
+              cp->scalar, c->d_err);
+  u.xs = g.xs; u.stats = c->d_stat;
   vc2_launch_unpack(c->L, u, n, c->stream);
 
   p.in = u.payload; p.in_stride = u.payload_stride; p.in_lens = u.lens; p.in_offs = d_offs;
@@ -2774,8 +2763,11 @@ static int transcode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_in
     }
   }
   vc2_launch_transcode_scale(c->L, p, n, c->stream);
-  return run_pack(c, g, n, d_store, p.qpack, qm, true, cp->prefix, cp->scalar, nullptr, nullptr, 0, (uint8_t *)d_out, (long long)stride_out,
-                  (unsigned long long *)d_lens_out, s16, d_storew);
+  PackJob job; // (no budgets: the output is a VBR payload whatever coded the input)
+  job.store = st; job.qidx = p.qpack; job.qm = qm;
+  job.prefix = cp->prefix; job.scalar = cp->scalar;
+  job.payload = (uint8_t *)d_out; job.stride = (long long)stride_out; job.lens = (unsigned long long *)d_lens_out;
+  return run_pack(c, g, n, job);
 }
 
 extern "C" int vc2hip_transcode_batch_dev(vc2hip_ctx *c, const void *d_payload_in, size_t payload_stride_in, const uint64_t *d_lens_in,

@@ -533,8 +533,8 @@ int vc2hip_decode_fields_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_
  * min(d_lens_in[i], payload_stride_in) is read; the bytes of an output slot past d_lens_out[i] are unspecified.  Pictures whose
  * decoded values leave the encoder's domain (|c| > 65534, an index of 116 .. 119) are held to those memory and isolation
  * rules only.
- * Not provided: LD, a change of prefix or scalar, a per-slice budget (HQ_CBR output), custom quantisation matrices, an option
- * of the command-line tools.  Extension, no counterpart in the reference. */
+ * Not provided: LD, custom quantisation matrices, an option of the command-line tools (a per-slice budget and a change of
+ * prefix or scalar: vc2hip_transcode_cbr_batch_dev below).  Extension, no counterpart in the reference. */
 typedef struct {
   int q_index;    /* the target: every slice ends at max(its own index, q_i); 0 .. VC2HIP_CAP_Q_TOP */
   int cap_bytes;  /* 0: no cap, q_i = q_index.  >= 1: per-picture cap on the output payload, q_i found on the device */
@@ -545,6 +545,49 @@ int vc2hip_transcode_batch_dev(vc2hip_ctx *ctx,
         const vc2hip_transcode_params *tp,
         void *d_payload_out, size_t payload_stride_out, uint64_t *d_lens_out,
         int32_t *d_qidx /* n x y_slices * x_slices output indices, raster order, or NULL */);
+
+/* Coded HQ pictures to a per-slice byte budget: HQ_CBR pictures out, for links that carry constant-bit-rate pictures (every
+ * slice of a fixed size, found without parsing).  Slots in and slots out, in the coefficient domain like the call above: no
+ * transform, no clip, no second rounding of a slice that already fits.  cp_out may change the prefix and the scalar.
+ * Per picture i, from slot[:min(d_lens_in[i], payload_stride_in)], with the budgets
+ * B = vc2hip_slice_bytes(y_slices, x_slices, cp_out->compressed_bytes, cp_out->scalar):
+ *   1. the slices are read at cp_in's prefix and scalar as vc2hip_decode_batch_dev reads them: quantised coefficients c and
+ *      every slice's own index q_s;
+ *   2. need_s = the bytes of slice s's values as they are: per component the SignedVLC bits through its last non-zero value,
+ *      in bytes, rounded up to cp_out's scalar (component_slice_bytes, Slices.cpp:97-119), summed over Y, U, V.  The slice is
+ *      KEPT iff every component's length byte is at most 255 and need_s <= B[s] - 4;
+ *   3. a kept slice ends at q'_s = q_s with its values untouched: no arithmetic is done on them;
+ *   4. every other slice is SEARCHED: C = scale(c, q_s), q'_s = what the HQ_CBR encoder's search (quantIndicesCBR,
+ *      EncodeStream.cpp:73-125) finds for the slice on C under B[s] and cp_out's scalar, its values quant(C, q'_s); default
+ *      quantisation matrix, per band max(q - matrix[band], 0) as everywhere;
+ *   5. the result is written as vc2hip_hq_pack writes HQ_CBR slices at cp_out's prefix and scalar: every picture is
+ *      sum(B) + slices * prefix bytes, which is d_lens_out[i].
+ * The keep rule makes the call stable across generations: its output fed to it again under the same cp_out comes back byte
+ * for byte (every slice is kept), and so does an HQ_CBR input at its own budget, prefix and scalar.
+ *   fmt, cp_in   the CODED pictures': VC2HIP_HQ_CONSTQ, HQ_CBR (which may take the budget-claim index) and HQ_CAPPED
+ *   cp_out       mode VC2HIP_HQ_CBR; kernel, depth, y_slices, x_slices as cp_in; its own compressed_bytes, prefix, scalar
+ *   d_qidx       n x y_slices * x_slices int32, raster order, or NULL: q'_s of every output slice
+ * The batch calls' contract above, word for word, as for vc2hip_transcode_batch_dev; "the first call" is the first of a
+ * geometry, n and budget.  The budget table is uploaded at first sight or on a change of its key; this call keeps two, an
+ * HQ_CBR input's claim and the output's budgets, each under its own key, so that once both are warm no call waits.
+ * VC2HIP_EINVAL, nothing launched, no output byte touched: a null pointer (d_qidx excepted); n < 1; cp_in or cp_out in LD mode;
+ * cp_out->mode != VC2HIP_HQ_CBR; cp_out differing from cp_in in kernel, depth or slice counts; cp_out->compressed_bytes < 1,
+ * scalar < 1 or prefix < 0; misalignment; output slots that overlap the input slots; a geometry the decoder refuses.
+ * VC2HIP_ECAP, on the host: payload_stride_out below the budgets' sum, as vc2hip_encode_batch_dev under cp_out.
+ * At vc2hip_sync the call refuses as its parts refuse, the reader first: VC2HIP_ESTREAM (once the reader has refused, what the
+ * search and the writer made of the rest is not reported: vc2hip_sync returns one code), VC2HIP_EQINDEX (the dequantiser, a
+ * search trial whose adjusted index passes 119), VC2HIP_ESCALAR (a search trial), VC2HIP_ECBR_TOOBIG / VC2HIP_ECBR_LEN (the
+ * CBR writer: e.g. a roomy budget whose V padding passes 255 * scalar).  Memory and isolation rules, and the pictures
+ * outside the encoder's domain, as for the call above.
+ * Not provided: LD, custom quantisation matrices, an option of the command-line tools.  Extension, no counterpart in the
+ * reference. */
+int vc2hip_transcode_cbr_batch_dev(vc2hip_ctx *ctx,
+        const void *d_payload_in, size_t payload_stride_in, const uint64_t *d_lens_in, int n,
+        const vc2hip_picture_format *fmt,
+        const vc2hip_coding_params *cp_in,   /* the coded pictures': HQ_CONSTQ, HQ_CBR (may take the budget claim), HQ_CAPPED */
+        const vc2hip_coding_params *cp_out,  /* mode HQ_CBR; kernel, depth, y_slices, x_slices as cp_in; own compressed_bytes, prefix, scalar */
+        void *d_payload_out, size_t payload_stride_out, uint64_t *d_lens_out,
+        int32_t *d_qidx /* n x y_slices * x_slices: q'_s, raster order, or NULL */);
 
 /* ---------------------------------------------------------------------------------------------
  * VC-2 streams in device memory: the picture data units around the slots of the batch calls

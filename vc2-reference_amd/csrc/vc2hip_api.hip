@@ -136,6 +136,7 @@ enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS,
        B_CAPTAB,            // HQ_CAPPED: the per-picture length table (vc2hip_cap.h)
        B_PKIN, B_PKOUT,     // vc2hip_set_packed_format: the planar staging of a call's input and of its output pictures
        B_TCLEN, B_TCQ,      // vc2hip_transcode_batch_dev: the indices handed to the slice coder, the pictures' indices of the capped form
+       B_CBRB2, B_CBRO2,    // budget_tables' second slot: the output side of vc2hip_transcode_cbr_batch_dev
        B_COUNT };
 
 struct vc2hip_ctx {
@@ -153,8 +154,8 @@ struct vc2hip_ctx {
   Launcher L;
   std::string err;
   // cached CBR / LD slice-size tables (re-uploaded only when the parameters change)
-  int cbr_key[5] = {-1, -1, -1, -1, -1};
-  uint64_t cbr_total = 0;
+  int cbr_key[2][5] = {{-1, -1, -1, -1, -1}, {-1, -1, -1, -1, -1}}; // (two slots: budget_tables)
+  uint64_t cbr_total[2] = {0, 0};
   int plane_qm_key[2] = {-1, -1}; // (kernel, depth) of the quantisation matrix in B_PLANE_QM (whole-plane inverse path)
   int debug_skip = 0;
   // VBR payload assembly.  Default: fixed-stride slots + scan + compaction (three launches).
@@ -1566,6 +1567,9 @@ static int store_to_planes(vc2hip_ctx *c, const Geom &g, const int32_t *d_store,
 }
 
 // The one owner of the context's budget tables (B_CBRB, B_CBRO, cbr_total) and of the key that says what they hold.
+// Two slots, each with its own buffers, key and total under the same rule: slot 0 is every call's; slot 1 holds the OUTPUT's
+// budgets of vc2hip_transcode_cbr_batch_dev, whose HQ_CBR input may claim its offsets from another budget's tables in the same
+// call -- one slot would upload and wait in every such call, and could not be captured into a graph.
 // HQ_CBR: the budgets of vc2hip_slice_bytes(ys, xs, compressed_bytes, scalar), each slice `prefix` bytes behind the one before.
 // LD: scalar 1 and prefix LD_BUDGETS (EncodeStream.cpp:509-512, DecodeStream.cpp:312, :331-333) -- the offsets carry no prefix.
 // Both are uploaded only when the key differs from the cached one or the buffer is gone: no copy and no wait in any later call.
@@ -1574,11 +1578,14 @@ static int store_to_planes(vc2hip_ctx *c, const Geom &g, const int32_t *d_store,
 // allocation, a copy) leaves no mode another mode's tables.  vc2hip_slice_bytes refuses ys, xs or scalar below 1 and nothing
 // else; every caller's entry checks hold all three (make_geom / stream_cp_ok, encode_check / decode_check; LD passes 1).
 enum { LD_BUDGETS = -7 };
-static int budget_tables(vc2hip_ctx *c, int ys, int xs, int compressed_bytes, int scalar, int prefix, Budgets &b, const int32_t *given = nullptr) {
+static int budget_tables(vc2hip_ctx *c, int ys, int xs, int compressed_bytes, int scalar, int prefix, Budgets &b, const int32_t *given = nullptr,
+                         int slot = 0) {
   const int ns = ys * xs;
   const int key[5] = {ys, xs, compressed_bytes, scalar, prefix};
-  if (given || memcmp(key, c->cbr_key, sizeof key) || !c->buf[B_CBRB].p) {
-    c->cbr_key[0] = -1; // whatever was cached is overwritten
+  const int id_bytes = slot ? B_CBRB2 : B_CBRB, id_offs = slot ? B_CBRO2 : B_CBRO;
+  int *const cached = c->cbr_key[slot];
+  if (given || memcmp(key, cached, sizeof key) || !c->buf[id_bytes].p) {
+    cached[0] = -1; // whatever was cached is overwritten
     std::vector<int32_t> made;
     if (!given) {
       made.resize(ns);
@@ -1589,15 +1596,15 @@ static int budget_tables(vc2hip_ctx *c, int ys, int xs, int compressed_bytes, in
     uint64_t run = 0;
     for (int i = 0; i < ns; ++i) { offs[i] = (uint32_t)run; run += (uint64_t)bytes[i] + (prefix == LD_BUDGETS ? 0 : prefix); }
     int32_t *db; uint32_t *dof;
-    NEED(c, B_CBRB, (size_t)ns * 4, db);
-    NEED(c, B_CBRO, (size_t)ns * 4, dof);
+    NEED(c, id_bytes, (size_t)ns * 4, db);
+    NEED(c, id_offs, (size_t)ns * 4, dof);
     HIPCHK(c, hipMemcpyAsync(db, bytes, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dof, offs.data(), (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the tables live on this function's stack)
-    c->cbr_total = run;
-    if (!given) memcpy(c->cbr_key, key, sizeof key);
+    c->cbr_total[slot] = run;
+    if (!given) memcpy(cached, key, sizeof key);
   }
-  b = Budgets{(const int32_t *)c->buf[B_CBRB].p, (const uint32_t *)c->buf[B_CBRO].p, c->cbr_total};
+  b = Budgets{(const int32_t *)c->buf[id_bytes].p, (const uint32_t *)c->buf[id_offs].p, c->cbr_total[slot]};
   return VC2HIP_OK;
 }
 
@@ -2796,6 +2803,91 @@ extern "C" int vc2hip_transcode_batch_dev(vc2hip_ctx *c, const void *d_payload_i
   return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
     return transcode_batch_common(l, g, at[0], payload_stride_in, (const uint64_t *)at[1], count, cp, tp, at[2], payload_stride_out,
                                   (uint64_t *)at[3], (int32_t *)at[4]);
+  });
+}
+
+// vc2hip_transcode_cbr_batch_dev (include/vc2hip.h): slots in, HQ_CBR slots out, through the coefficient
+// store and no further.  The slice index and the slice reader at cp_in's prefix and scalar; k_transcode_fit keeps the slices
+// that fit cp_out's budgets as they are and dequantises the others; the HQ_CBR search over those alone; the slice coder in its
+// CBR form at cp_out's prefix and scalar; k_transcode_settle for d_qidx and the order of the refusals.  No transform runs.
+// Two budget tables may be alive at once: an HQ_CBR input's claim (slot 0) and the output's budgets (slot 1).
+static int transcode_cbr_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_in, size_t stride_in, const uint64_t *d_lens_in, int n,
+                                      const vc2hip_coding_params *cp_in, const vc2hip_coding_params *cp_out, void *d_out,
+                                      size_t stride_out, uint64_t *d_lens_out, int32_t *d_qidx) {
+  ENTER(c);
+  int rc;
+  const int ns = g.ys * g.xs;
+  int32_t qm[VC2_MAX_BANDS];
+  if ((rc = vc2hip_quant_matrix(cp_in->kernel, cp_in->depth, qm))) return set_err(c, rc);
+  Budgets out_b;
+  if ((rc = budget_tables(c, g.ys, g.xs, cp_out->compressed_bytes, cp_out->scalar, cp_out->prefix, out_b, nullptr, 1))) return rc;
+  if (stride_out < out_b.total) return set_err(c, VC2HIP_ECAP); // (what vc2hip_encode_batch_dev asks under cp_out; before any launch)
+  const bool s16 = use_store16(c, g, cp_in->kernel);
+  const long long sstride = record_stride(g);
+  TranscodeParams p;
+  memset(&p, 0, sizeof p);
+  int32_t *d_store, *d_storew = nullptr, *d_q;
+  NEED(c, B_STORE, (size_t)n * sstride * 4, d_store);
+  if (s16) NEED(c, B_STOREW, (size_t)n * sstride * 4, d_storew);
+  NEED(c, B_QIDX, (size_t)n * ns * 4, d_q);
+  NEED(c, B_TCLEN, (size_t)n * ns * 4, p.qpack);
+  const Store st = {d_store, d_storew, s16, sstride};
+  uint32_t *d_offs;
+  if ((rc = build_index(c, (const uint8_t *)d_in, (long long)stride_in, (const unsigned long long *)d_lens_in, n, ns, cp_in->prefix,
+                        cp_in->scalar, &d_offs, cbr_claim_tables(c, g, cp_in)))) return rc;
+  UnpackParams u;
+  fill_unpack(u, g, (const uint8_t *)d_in, (long long)stride_in, (const unsigned long long *)d_lens_in, d_offs, st, d_q, cp_in->prefix,
+              cp_in->scalar, c->d_err);
+  u.xs = g.xs; u.stats = c->d_stat;
+  vc2_launch_unpack(c->L, u, n, c->stream);
+
+  p.store = d_store; p.store_wide = d_storew; p.store16 = s16; p.store_stride = sstride;
+  p.slice_coefs = g.slice_coefs; p.qs = d_q; p.qidx_out = d_qidx;
+  p.n_slices = ns;
+  fill_comp_arrays(g, p.comp_n, p.comp_off, p.comp_n0);
+  p.prefix = cp_out->prefix; p.scalar = cp_out->scalar;
+  p.out_budgets = out_b.bytes; p.out_scalar = cp_out->scalar;
+  p.qm_min = qm[0];
+  for (int b = 0; b < 3 * g.depth + 1; ++b) { p.qmatrix[b] = qm[b]; p.qm_min = std::min(p.qm_min, (int)qm[b]); }
+  p.err = c->d_err;
+  vc2_launch_transcode_fit(c->L, p, n, c->stream);
+  CbrParams s;
+  fill_cbr(s, g, st, p.qpack, out_b.bytes, cp_out->scalar, qm, c->cbr_general, c->d_err);
+  vc2_launch_cbr_marked(c->L, s, n, c->stream);
+  PackJob job;
+  job.store = st; job.qidx = p.qpack; job.qm = qm;
+  job.prefix = cp_out->prefix; job.scalar = cp_out->scalar; job.budgets = out_b;
+  job.payload = (uint8_t *)d_out; job.stride = (long long)stride_out; job.lens = (unsigned long long *)d_lens_out;
+  if ((rc = run_pack(c, g, n, job))) return rc;
+  vc2_launch_transcode_settle(c->L, p, n, c->stream);
+  return VC2HIP_OK;
+}
+
+extern "C" int vc2hip_transcode_cbr_batch_dev(vc2hip_ctx *c, const void *d_payload_in, size_t payload_stride_in, const uint64_t *d_lens_in,
+                                              int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp_in,
+                                              const vc2hip_coding_params *cp_out, void *d_payload_out, size_t payload_stride_out,
+                                              uint64_t *d_lens_out, int32_t *d_qidx) {
+  if (int rc = batch_args(c, n, f, cp_in, payload_stride_in,
+                          {{d_payload_in, 16}, {d_lens_in, 8}, {d_payload_out, 16}, {d_lens_out, 8}, {d_qidx, 4, true}})) return rc;
+  if (!cp_out) return set_err(c, VC2HIP_EINVAL);
+  if (payload_stride_out & 15) return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
+  if (cp_in->mode != VC2HIP_HQ_CONSTQ && cp_in->mode != VC2HIP_HQ_CBR && cp_in->mode != VC2HIP_HQ_CAPPED)
+    return set_err(c, VC2HIP_EINVAL, "transcode_cbr_batch_dev: HQ pictures only");
+  if (cp_out->mode != VC2HIP_HQ_CBR) return set_err(c, VC2HIP_EINVAL, "transcode_cbr_batch_dev: cp_out must be HQ_CBR");
+  if (cp_out->kernel != cp_in->kernel || cp_out->depth != cp_in->depth || cp_out->y_slices != cp_in->y_slices || cp_out->x_slices != cp_in->x_slices)
+    return set_err(c, VC2HIP_EINVAL, "transcode_cbr_batch_dev: cp_out must have cp_in's kernel, depth and slice counts");
+  if (cp_out->compressed_bytes < 1 || cp_out->scalar < 1 || cp_out->prefix < 0)
+    return set_err(c, VC2HIP_EINVAL, "transcode_cbr_batch_dev: cp_out needs compressed_bytes >= 1, scalar >= 1, prefix >= 0");
+  Geom g;
+  if (int rc = decode_check(c, f, cp_in, d_lens_in, false, g)) return rc;
+  const uint8_t *in8 = (const uint8_t *)d_payload_in, *out8 = (const uint8_t *)d_payload_out;
+  if (out8 < in8 + (size_t)n * payload_stride_in && in8 < out8 + (size_t)n * payload_stride_out)
+    return set_err(c, VC2HIP_EINVAL, "transcode_cbr_batch_dev: the output slots overlap the input slots");
+  const BatchBuf bufs[] = {{d_payload_in, payload_stride_in, false}, {d_lens_in, 8, false}, {d_payload_out, payload_stride_out, true},
+                           {d_lens_out, 8, true}, {d_qidx, (size_t)g.ys * g.xs * 4, true}};
+  return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
+    return transcode_cbr_batch_common(l, g, at[0], payload_stride_in, (const uint64_t *)at[1], count, cp_in, cp_out, at[2],
+                                      payload_stride_out, (uint64_t *)at[3], (int32_t *)at[4]);
   });
 }
 

@@ -74,6 +74,8 @@ __global__ __launch_bounds__(256, VC2_CBR16_WPE) void k_cbr_search16(const CbrPa
   const int m_y = 16 * (int)(lq & 0xFFu), m_c = 16 * (int)((lq >> 8) & 0xFFu), m_h = 16 * (int)((lq >> 16) & 0xFFu);
   int guess = -1; // the previous slice's threshold
   for (int slice = slice0; slice < min(slice0 + CBR_SPW, p.n_slices); ++slice) { // no workgroup barriers below
+  // (vc2_launch_cbr_marked: only the marked slices are searched; the guess is a starting point, whichever slice left it)
+  if (p.only_marked == 2 && p.qidx[(size_t)pic * p.n_slices + slice] != VC2_CBR_MARK) continue;
   const size_t rec_at = (size_t)pic * p.store_stride + (size_t)slice * p.slice_coefs;
   const int16_t *rec = (const int16_t *)p.store + rec_at;
   float fy[8], fc[8], fh = 0.f; // |coefficient|

@@ -317,7 +317,10 @@ struct CbrParams {
   int n_bands;
   int qmatrix[VC2_MAX_BANDS];
   unsigned *err;
-  int only_marked;            // set by the launcher: search only the slices whose index is VC2_CBR_MARK
+  int only_marked;            // set by the launcher: search only the slices whose index is VC2_CBR_MARK (1: a small grid walks the
+                              // picture for the few there are; 2: a wavefront per slice, as many may be marked as not)
+  int clamp_refused;          // set by vc2_launch_cbr_marked: a slice the general kernel refuses at its first trial is left at
+                              // 119 + qm_min, not 127 -- the slice coder behind the search then raises no error of its own
   int general_only;           // VC2HIP_FLAG_CBR_GENERAL: no register kernel (tests, A/B)
   float inv_scalar;           // set by the launcher
   int qm_min;                 // set by the launcher: the smallest matrix entry
@@ -548,11 +551,22 @@ struct TranscodeParams {
   int qmatrix[VC2_MAX_BANDS];
   int qm_min;                     // the smallest matrix entry: a slice's index q is refused when q - qm_min > 119, as the decoder refuses it
   unsigned *err;
+  // vc2hip_transcode_cbr_batch_dev: the output's budgets, one picture's worth, and its size scalar
+  const int32_t *out_budgets;
+  int out_scalar;
 };
 void vc2_upload_tables_transcode(const QuantTables &t, hipStream_t s);
 void vc2_launch_transcode_measure(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_transcode_pick(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_transcode_scale(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
+// To a per-slice byte budget (vc2hip_transcode_cbr_batch_dev): between the slice reader and the HQ_CBR search.  A slice whose
+// values fit its budget as they are is KEPT (qpack: its index - 256, the coder's identity); every other slice is
+// dequantised in place and marked for the search (qpack: VC2_CBR_MARK, which vc2_launch_cbr_marked replaces).
+void vc2_launch_transcode_fit(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
+// Behind the slice coder: d_qidx from qpack, and the order of the composition's refusals (the reader's comes first)
+void vc2_launch_transcode_settle(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s);
+// The HQ_CBR search (vc2_launch_cbr's general kernel) over the slices whose index is VC2_CBR_MARK and no other
+void vc2_launch_cbr_marked(Launcher &L, const CbrParams &p, int n_pictures, hipStream_t s);
 
 // packed and semi-planar pictures <-> planar staging (vc2hip_packed.hip, vc2hip_set_packed_format)
 struct PackedParams {

@@ -1305,11 +1305,15 @@ __global__ __launch_bounds__(256) void k_cbr_search(const CbrParams p) {
     q = trial - 1;
   }
   if (__any(bad_q) && lane == 0) atomicOr(p.err, VC2_DEVERR_QINDEX);
+  // (vc2_launch_cbr_marked: a slice refused at its first trial leaves 127, which the slice coder behind this search would
+  // refuse with VC2_DEVERR_QINDEX -- ahead of this slice's own VC2_DEVERR_SCALAR in vc2hip_sync's order.  The picture is
+  // refused either way; the coder is handed the largest index it takes)
+  if (bad && p.clamp_refused) q = min(q, 119 + p.qm_min);
   if (lane == 0) p.qidx[(size_t)pic * p.n_slices + slice] = q;
   wave_lds_sync();
   }; // search(slice)
-  if (!p.only_marked) {
-    if (slice < p.n_slices) search(slice);
+  if (p.only_marked != 1) { // (2: the full grid, every wavefront its own slice if that slice is marked -- vc2_launch_cbr_marked)
+    if (slice < p.n_slices && (!p.only_marked || p.qidx[(size_t)pic * p.n_slices + slice] == VC2_CBR_MARK)) search(slice);
     return;
   }
   // 64 indices per look: the wavefronts of the small grid stride over the picture's slices
@@ -1354,6 +1358,8 @@ __global__ __launch_bounds__(256) void k_cbr_search_reg(const CbrParams p) {
   const bool has_y = jy < p.comp_n[0], has_c = jc < p.comp_n[1];
   int guess = -1; // the previous slice's threshold (see the search below)
   for (int slice = slice0; slice < min(slice0 + CBR_SPW, p.n_slices); ++slice) { // no workgroup barriers below
+  // (vc2_launch_cbr_marked: only the marked slices are searched; the guess is a starting point, whichever slice left it)
+  if (p.only_marked == 2 && p.qidx[(size_t)pic * p.n_slices + slice] != VC2_CBR_MARK) continue;
   const size_t rec_at = (size_t)pic * p.store_stride + (size_t)slice * p.slice_coefs;
   const ST *rec = (const ST *)p.store + rec_at;
   const int32_t *recw = St<ST>::narrow ? p.store_wide + rec_at : nullptr;
@@ -1511,10 +1517,37 @@ int vc2_waves_for_lds(size_t per_wave) {
   const size_t w = (size_t)(160 * 1024) / per_wave;
   return (int)std::min<size_t>(4, w);
 }
+// the geometries the register kernels take (and VC2HIP_FLAG_CBR_GENERAL, which keeps every geometry from them)
+static bool cbr_reg_geometry(const CbrParams &p) {
+  return !p.general_only && p.comp_n[0] <= 512 && p.comp_n[1] <= 256 && p.comp_n[1] == p.comp_n[2] && p.n_bands <= 32 &&
+         p.comp_n[0] % 8 == 0 && p.comp_n[1] % 8 == 0 && (p.store_stride % 8) == 0 && (p.slice_coefs % 8) == 0 &&
+         p.comp_off[1] % 8 == 0 && p.comp_off[2] % 8 == 0;
+}
+// the general kernel's launch; only_marked 1: a small grid over the few slices the register kernel handed back
+static void launch_cbr_general(Launcher &L, const CbrParams &p, int n_pictures, hipStream_t s) {
+  const size_t per_wave = (size_t)p.slice_coefs * 4 + 32 * 16, tables = 768; // + the wavefront's quantiser table; + band tables
+  const bool few = p.only_marked == 1;
+  if (per_wave + tables > 160 * 1024) { // the slice does not fit in LDS: the search reads it from the store in every trial
+    const int wpw = 4;
+    const size_t lds = tables + wpw * 32 * 16;
+    const int gx = few ? std::min((p.n_slices + wpw - 1) / wpw, 64) : (p.n_slices + wpw - 1) / wpw;
+    if (p.store16) VC2_LAUNCH(L, (k_cbr_search<int16_t, true>), dim3(gx, n_pictures), dim3(64 * wpw), lds, s, p);
+    else VC2_LAUNCH(L, (k_cbr_search<int32_t, true>), dim3(gx, n_pictures), dim3(64 * wpw), lds, s, p);
+    return;
+  }
+  const int wpw = std::max(1, std::min(4, (int)((160 * 1024 - tables) / per_wave)));
+  const int gx = few ? std::min((p.n_slices + wpw - 1) / wpw, 64) : (p.n_slices + wpw - 1) / wpw;
+  if (p.store16) {
+    vc2_allow_lds((const void *)k_cbr_search<int16_t>, 160 * 1024);
+    VC2_LAUNCH(L, k_cbr_search<int16_t>, dim3(gx, n_pictures), dim3(64 * wpw), wpw * per_wave + tables, s, p);
+  } else {
+    vc2_allow_lds((const void *)k_cbr_search<int32_t>, 160 * 1024);
+    VC2_LAUNCH(L, k_cbr_search<int32_t>, dim3(gx, n_pictures), dim3(64 * wpw), wpw * per_wave + tables, s, p);
+  }
+}
 void vc2_launch_cbr(Launcher &L, const CbrParams &p0, int n_pictures, hipStream_t s) {
   CbrParams p = p0;
   fill_band_lut(p.band_lut, p.comp_n, p.comp_n0);
-  const size_t per_wave = (size_t)p.slice_coefs * 4 + 32 * 16, tables = 768; // + the wavefront's quantiser table; + band tables
   vc2_prof_begin(L, "cbr_search", s);
   p.only_marked = 0;
   p.qm_min = p.qmatrix[0];
@@ -1522,9 +1555,7 @@ void vc2_launch_cbr(Launcher &L, const CbrParams &p0, int n_pictures, hipStream_
   p.inv_scalar = 1.0f / (float)p.scalar; // the smallest float >= 1 / scalar
   if ((double)p.inv_scalar < 1.0 / (double)p.scalar) p.inv_scalar = nextafterf(p.inv_scalar, INFINITY);
   // (general_only = VC2HIP_FLAG_CBR_GENERAL: A/B and test switch, the general kernel only)
-  const bool reg = !p.general_only && p.comp_n[0] <= 512 && p.comp_n[1] <= 256 && p.comp_n[1] == p.comp_n[2] && p.n_bands <= 32 &&
-                   p.comp_n[0] % 8 == 0 && p.comp_n[1] % 8 == 0 && (p.store_stride % 8) == 0 && (p.slice_coefs % 8) == 0 &&
-                   p.comp_off[1] % 8 == 0 && p.comp_off[2] % 8 == 0;
+  const bool reg = cbr_reg_geometry(p);
   if (reg) { // the register kernel, then the general one over the slices it handed back (usually none: a small grid)
     const int per_wg = 4 * CBR_SPW; // slices per workgroup
     static const int use16 = vc2_tune_int("VC2HIP_CBR16", 1);
@@ -1535,24 +1566,32 @@ void vc2_launch_cbr(Launcher &L, const CbrParams &p0, int n_pictures, hipStream_
     else VC2_LAUNCH(L, k_cbr_search_reg<int32_t>, dim3((p.n_slices + per_wg - 1) / per_wg, n_pictures), dim3(256), 0, s, p);
     p.only_marked = 1;
   }
-  if (per_wave + tables > 160 * 1024) { // the slice does not fit in LDS: the search reads it from the store in every trial
-    const int wpw = 4;
-    const size_t lds = tables + wpw * 32 * 16;
-    const int gx = p.only_marked ? std::min((p.n_slices + wpw - 1) / wpw, 64) : (p.n_slices + wpw - 1) / wpw;
-    if (p.store16) VC2_LAUNCH(L, (k_cbr_search<int16_t, true>), dim3(gx, n_pictures), dim3(64 * wpw), lds, s, p);
-    else VC2_LAUNCH(L, (k_cbr_search<int32_t, true>), dim3(gx, n_pictures), dim3(64 * wpw), lds, s, p);
-    vc2_prof_end(L, s);
-    return;
+  launch_cbr_general(L, p, n_pictures, s);
+  vc2_prof_end(L, s);
+}
+// vc2hip_transcode_cbr_batch_dev: the slices transcode_fit marked and no other, which may be most of a picture or none of it.
+// vc2_launch_cbr's kernels on their full grids, told to pass over what is not marked (only_marked 2): the register kernel
+// where the geometry has one, then the general kernel over what that handed back; the general kernel alone elsewhere.
+void vc2_launch_cbr_marked(Launcher &L, const CbrParams &p0, int n_pictures, hipStream_t s) {
+  CbrParams p = p0;
+  fill_band_lut(p.band_lut, p.comp_n, p.comp_n0);
+  vc2_prof_begin(L, "cbr_search", s);
+  p.only_marked = 2;
+  p.clamp_refused = 1;
+  p.qm_min = p.qmatrix[0];
+  for (int b = 1; b < p.n_bands; ++b) p.qm_min = std::min(p.qm_min, p.qmatrix[b]);
+  p.inv_scalar = 1.0f / (float)p.scalar; // the smallest float >= 1 / scalar
+  if ((double)p.inv_scalar < 1.0 / (double)p.scalar) p.inv_scalar = nextafterf(p.inv_scalar, INFINITY);
+  if (cbr_reg_geometry(p)) {
+    const dim3 grid((p.n_slices + 4 * CBR_SPW - 1) / (4 * CBR_SPW), n_pictures);
+    static const int use16 = vc2_tune_int("VC2HIP_CBR16", 1);
+    CbrParams p16 = p;
+    if (use16 && cbr16_plan(p16, p16.lane8)) VC2_LAUNCH(L, k_cbr_search16, grid, dim3(256), 0, s, p16);
+    else if (p.store16) VC2_LAUNCH(L, k_cbr_search_reg<int16_t>, grid, dim3(256), 0, s, p);
+    else VC2_LAUNCH(L, k_cbr_search_reg<int32_t>, grid, dim3(256), 0, s, p);
+    p.only_marked = 1;
   }
-  const int wpw = std::max(1, std::min(4, (int)((160 * 1024 - tables) / per_wave)));
-  const int gx = p.only_marked ? std::min((p.n_slices + wpw - 1) / wpw, 64) : (p.n_slices + wpw - 1) / wpw;
-  if (p.store16) {
-    vc2_allow_lds((const void *)k_cbr_search<int16_t>, 160 * 1024);
-    VC2_LAUNCH(L, k_cbr_search<int16_t>, dim3(gx, n_pictures), dim3(64 * wpw), wpw * per_wave + tables, s, p);
-  } else {
-    vc2_allow_lds((const void *)k_cbr_search<int32_t>, 160 * 1024);
-    VC2_LAUNCH(L, k_cbr_search<int32_t>, dim3(gx, n_pictures), dim3(64 * wpw), wpw * per_wave + tables, s, p);
-  }
+  launch_cbr_general(L, p, n_pictures, s);
   vc2_prof_end(L, s);
 }
 

@@ -19,6 +19,12 @@
 //   transcode_pick     the picture's index from the table of candidate lengths, two rounds (vc2hip_cap.h's rule)
 // The measuring reader is bounded to the component, bits past the bound read as 1; every input address is clamped to
 // min(d_lens[i], stride).
+// To a per-slice byte budget (vc2hip_transcode_cbr_batch_dev) the same reader is followed by
+//   transcode_fit      one wavefront per slice: the bytes the slice's values need as they are; a slice that fits its HQ_CBR
+//                      budget is kept (q_s - 256 again), every other one is dequantised in place and marked
+//   cbr_search (...)   the encoder's HQ_CBR search over the marked slices alone (vc2_launch_cbr_marked, vc2hip_slices.hip)
+//   hq_pack (...)      the slice coder in its CBR form, at the output's prefix and scalar
+//   transcode_settle   d_qidx, and the reader's refusal ahead of what the coders made of a broken picture
 #include "vc2hip_internal.h"
 #include "vc2hip_store.h"
 
@@ -461,7 +467,145 @@ __global__ __launch_bounds__(256) void k_transcode_scale(const TranscodeParams p
   }
 }
 
+// vc2hip_transcode_cbr_batch_dev: which slices fit their HQ_CBR budget as they are, and the others
+// made ready for the search.  One wavefront per slice, TF_WAVES slices a workgroup, a lane takes every 64th piece of G
+// coefficients (16 bytes: 8 of the 16-bit store, 4 of the int32 store; 1 where a record is not made of whole pieces).
+// A record holds its components' coefficients in coded order, so per component
+//   count = bits through the last non-zero value = sum over the non-zero values of (SignedVLC bits - 1) + its position + 1
+// (a zero is one bit): a sum and a maximum, reduced over the lanes by shuffles -- no second look at the values, no atomics.
+//   need = sum over Y, U, V of ceil(ceil(count / 8) / scalar) * scalar          (component_slice_bytes, Slices.cpp:97-119)
+// A slice is KEPT iff every length byte is at most 255 and need <= budget - 4: its values stay as they are and the coder is
+// handed q_s - 256 (k_transcode_scale's identity: header byte q_s, adjusted index 0).  Every other slice is dequantised in
+// place, scale(c, q_s), from the pieces the lane still holds (TF_HOLD of them: slices of up to 64 * TF_HOLD * G coefficients
+// are read once; what lies beyond is read again), and marked for the search (VC2_CBR_MARK).
+constexpr int TF_WAVES = 4, TF_HOLD = 2;
+__device__ __forceinline__ int tf_wave_sum(int v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ int tf_wave_max(int v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m));
+  return v;
+}
+template <class ST, int G>
+__global__ __launch_bounds__(64 * TF_WAVES) void k_transcode_fit(const TranscodeParams p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int pic = blockIdx.y, slice = blockIdx.x * TF_WAVES + wave;
+  if (slice >= p.n_slices) return; // (no workgroup barrier below)
+  const size_t sidx = (size_t)pic * p.n_slices + slice;
+  const int qs = p.qs[sidx], gps = p.slice_coefs / G;
+  const size_t rec = (size_t)pic * p.store_stride + (size_t)slice * p.slice_coefs;
+  ST *const st = (ST *)p.store + rec;
+  int32_t *const wide = p.store_wide ? p.store_wide + rec : nullptr;
+  auto load = [&](int g, int (&e)[G]) {
+    if constexpr (G == 8) St<ST>::load8(st + g * 8, wide ? wide + g * 8 : nullptr, e);
+    else if constexpr (G == 4) St<ST>::load4(st + g * 4, wide ? wide + g * 4 : nullptr, e);
+    else e[0] = St<ST>::load1(st + g, wide ? wide + g : nullptr);
+  };
+  auto comp_of = [&](int e0) -> int { return e0 >= p.comp_off[2] ? 2 : e0 >= p.comp_off[1] ? 1 : 0; }; // (a piece lies in one component)
+  int d0 = 0, d1 = 0, d2 = 0, l0 = -1, l1 = -1, l2 = -1; // per component: sum of (bits - 1) over the non-zero values, the last one's position
+  auto measure = [&](int g, const int (&e)[G]) {
+    const int comp = comp_of(g * G), j0 = g * G - p.comp_off[comp], n = p.comp_n[comp];
+    int d = 0, l = -1;
+#pragma unroll
+    for (int k = 0; k < G; ++k)
+      if (e[k] != 0 && j0 + k < n) { d += tc_bits(e[k]) - 1; l = j0 + k; }
+    d0 += comp == 0 ? d : 0; d1 += comp == 1 ? d : 0; d2 += comp == 2 ? d : 0;
+    l0 = max(l0, comp == 0 ? l : -1); l1 = max(l1, comp == 1 ? l : -1); l2 = max(l2, comp == 2 ? l : -1);
+  };
+  int held[TF_HOLD][G];
+#pragma unroll
+  for (int h = 0; h < TF_HOLD; ++h) {
+#pragma unroll
+    for (int k = 0; k < G; ++k) held[h][k] = 0;
+    const int g = lane + 64 * h;
+    if (g < gps) { load(g, held[h]); measure(g, held[h]); }
+  }
+#pragma unroll 1 // (unrolled, the int32 instantiations took 207 registers for a loop that most geometries never enter)
+  for (int g = lane + 64 * TF_HOLD; g < gps; g += 64) {
+    int e[G];
+    load(g, e);
+    measure(g, e);
+  }
+  d0 = tf_wave_sum(d0); d1 = tf_wave_sum(d1); d2 = tf_wave_sum(d2);
+  l0 = tf_wave_max(l0); l1 = tf_wave_max(l1); l2 = tf_wave_max(l2);
+  const int sc = p.out_scalar;
+  auto length_byte = [&](int d, int l) -> int { return (((l >= 0 ? d + l + 1 : 0) + 7) / 8 + sc - 1) / sc; };
+  const int b0 = length_byte(d0, l0), b1 = length_byte(d1, l1), b2 = length_byte(d2, l2);
+  const bool keep = max(b0, max(b1, b2)) <= 255 && (b0 + b1 + b2) * sc <= p.out_budgets[slice] - 4; // (the same in every lane)
+  if (lane == 0) {
+    p.qpack[sidx] = keep ? qs - 256 : VC2_CBR_MARK;
+    // the dequantiser's refusal (Quantisation.cpp:61), behind the reader's as in k_transcode_scale; a kept slice meets no dequantiser
+    if (!keep && qs - p.qm_min > 119 && !(__atomic_load_n(p.err, __ATOMIC_RELAXED) & VC2_DEVERR_STREAM)) atomicOr(p.err, VC2_DEVERR_QINDEX);
+  }
+  if (keep) return;
+  auto dequantise = [&](int g, int (&e)[G]) {
+    int any = 0;
+#pragma unroll
+    for (int k = 0; k < G; ++k) any |= e[k];
+    if (any == 0) return; // scale(0) is 0, and most coefficients of a coded picture are zero
+    const int comp = comp_of(g * G), j0 = g * G - p.comp_off[comp], n = p.comp_n[comp], n0 = p.comp_n0[comp];
+    const int n0s = n0 > 0 && (n0 & (n0 - 1)) == 0 ? 31 - __clz(n0) : -1;
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      if (j0 + k >= n) continue; // (what a record holds between its components stays)
+      const int mm = n0s >= 0 ? (j0 + k) >> n0s : (j0 + k) / n0;
+      int band = 0;
+      if (mm) { const int L = (31 - __clz(mm)) / 2 + 1; band = 3 * (L - 1) + (mm >> (2 * (L - 1))); }
+      const int aq = min(max(qs - p.qmatrix[band], 0), 119); // (beyond 119: refused above; the tables end there)
+      e[k] = tc_scale_c(e[k], c_qt.qf[aq], c_qt.off[aq]);
+    }
+    if constexpr (G == 8) St<ST>::store8(st + g * 8, wide ? wide + g * 8 : nullptr, e);
+    else if constexpr (G == 4) St<ST>::store4(st + g * 4, wide ? wide + g * 4 : nullptr, e[0], e[1], e[2], e[3]);
+    else St<ST>::store1(st + g, wide ? wide + g : nullptr, e[0]);
+  };
+#pragma unroll
+  for (int h = 0; h < TF_HOLD; ++h) {
+    const int g = lane + 64 * h;
+    if (g < gps) dequantise(g, held[h]);
+  }
+#pragma unroll 1
+  for (int g = lane + 64 * TF_HOLD; g < gps; g += 64) {
+    int e[G];
+    load(g, e);
+    dequantise(g, e);
+  }
+}
+
+// Behind the slice coder of vc2hip_transcode_cbr_batch_dev.  d_qidx: what the coder was handed, a kept slice's index put
+// back (q_s - 256 is the only negative entry).  And the order of the refusals: the search and the CBR writer have by now
+// worked on whatever a broken chain left in the store and may have refused it; the composition stops at its reader, and
+// vc2hip_sync returns ONE code for everything on the context since the last sync -- so once the error word holds
+// VC2_DEVERR_STREAM the coders' flags are taken out of it again.
+__global__ __launch_bounds__(256) void k_transcode_settle(const TranscodeParams p, int total) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (p.qidx_out && i < total) {
+    const int q = p.qpack[i];
+    p.qidx_out[i] = q < 0 ? q + 256 : q;
+  }
+  if (i == 0 && (__atomic_load_n(p.err, __ATOMIC_RELAXED) & VC2_DEVERR_STREAM))
+    atomicAnd(p.err, ~(unsigned)(VC2_DEVERR_QINDEX | VC2_DEVERR_SCALAR | VC2_DEVERR_CBR_TOOBIG | VC2_DEVERR_CBR_LEN | VC2_DEVERR_CODE32));
+}
+
 } // namespace
+
+void vc2_launch_transcode_fit(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s) {
+  vc2_prof_begin(L, "transcode_fit", s);
+  const dim3 grid((p.n_slices + TF_WAVES - 1) / TF_WAVES, n_pictures), block(64 * TF_WAVES);
+  const bool quads = p.slice_coefs % 4 == 0 && p.store_stride % 4 == 0 && p.comp_off[1] % 4 == 0 && p.comp_off[2] % 4 == 0;
+  if (p.store16) VC2_LAUNCH(L, (k_transcode_fit<int16_t, 8>), grid, block, 0, s, p);
+  else if (quads) VC2_LAUNCH(L, (k_transcode_fit<int32_t, 4>), grid, block, 0, s, p);
+  else VC2_LAUNCH(L, (k_transcode_fit<int32_t, 1>), grid, block, 0, s, p);
+  vc2_prof_end(L, s);
+}
+void vc2_launch_transcode_settle(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s) {
+  vc2_prof_begin(L, "transcode_settle", s);
+  const int total = n_pictures * p.n_slices;
+  VC2_LAUNCH(L, k_transcode_settle, dim3((total + 255) / 256), dim3(256), 0, s, p, total);
+  vc2_prof_end(L, s);
+}
 
 void vc2_launch_transcode_measure(Launcher &L, const TranscodeParams &p, int n_pictures, hipStream_t s) {
   vc2_prof_begin(L, "transcode_measure", s);

@@ -97,7 +97,7 @@ EXPORTS = [
     "vc2hip_encode_recon_batch_dev", "vc2hip_stream_write_fragments_dev",
     "vc2hip_set_sample_layout", "vc2hip_layout_picture_bytes",
     "vc2hip_set_packed_format", "vc2hip_packed_picture_bytes",
-    "vc2hip_transcode_batch_dev",
+    "vc2hip_transcode_batch_dev", "vc2hip_transcode_cbr_batch_dev",
 ]
 
 
@@ -165,6 +165,8 @@ def load_library():
                                                   vp, C.c_size_t, vp, vp, vp, vp]
     lib.vc2hip_transcode_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat), C.POINTER(CodingParams),
                                                C.POINTER(TranscodeParams), vp, C.c_size_t, vp, vp]
+    lib.vc2hip_transcode_cbr_batch_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(PictureFormat), C.POINTER(CodingParams),
+                                                   C.POINTER(CodingParams), vp, C.c_size_t, vp, vp]
     lib.vc2hip_set_sample_layout.argtypes = [vp, C.POINTER(SampleLayout)]
     lib.vc2hip_layout_picture_bytes.argtypes = [C.POINTER(PictureFormat), C.POINTER(SampleLayout)]
     lib.vc2hip_layout_picture_bytes.restype = C.c_size_t
@@ -522,6 +524,12 @@ class Vc2Hip:
         self._chk(self.lib.vc2hip_transcode_batch_dev(self.h, d_in, stride_in, d_lens_in, n, C.byref(fmt), C.byref(cp),
                                                       C.byref(tp) if tp is not None else None, d_out, stride_out, d_lens_out,
                                                       d_qidx))
+
+    # coded pictures to a per-slice byte budget, HQ_CBR slots out (vc2hip_transcode_cbr_batch_dev): cp_in is the coded pictures',
+    # cp_out an HQ_CBR coding_params of the same kernel, depth and slice counts with its own compressed_bytes, prefix and scalar
+    def transcode_cbr_batch_dev(self, d_in, stride_in, d_lens_in, n, fmt, cp_in, cp_out, d_out, stride_out, d_lens_out, d_qidx=None):
+        self._chk(self.lib.vc2hip_transcode_cbr_batch_dev(self.h, d_in, stride_in, d_lens_in, n, C.byref(fmt), C.byref(cp_in),
+                                                          C.byref(cp_out), d_out, stride_out, d_lens_out, d_qidx))
 
     # interlaced frames as field pictures: frame_fmt is the frame's format, cp one field's; 2 * n_frames slots in stream order
     def encode_fields_batch_dev(self, d_frames, n_frames, frame_fmt, top_field_first, cp, d_payload, stride, d_lens):

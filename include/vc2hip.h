@@ -47,7 +47,9 @@ enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2, VC2HIP_HQ_CAPPED 
  * picture alone; trying an index raises no error.  The indices are found on the device between the transform and the slice
  * coder: the batch contract (asynchronous, no allocation / host copy / wait after the first call of a geometry, graph
  * capture, vc2hip_set_streams, sample layouts, every context flag) holds unchanged.  Why 115: beyond it the reference's
- * 32-bit quantisation factors wrap and a payload's length is no longer monotonic in the index.
+ * 32-bit quantisation factors wrap and a payload's length is no longer monotonic in the index.  Under a matrix of the
+ * caller's (vc2hip_set_quant_matrix) the rule stays: a band's index max(q - m, 0) never exceeds q, so up to 115 every band's
+ * factor is a monotone one and the lengths stay monotone whatever the entries.
  * q_index outside 0 .. 115 or compressed_bytes < 1: VC2HIP_EINVAL, nothing launched.  Every call that does not encode
  * (decoders, vc2hip_picture_header, the stream calls, vc2hip_max_payload_bytes) reads the mode as HQ_CONSTQ: the stream is
  * a plain HQ VBR stream, and payload_stride >= vc2hip_max_payload_bytes as for HQ_CONSTQ.
@@ -277,8 +279,9 @@ int vc2hip_decode_picture_end(vc2hip_ctx *ctx, int ticket);
  *     of a geometry or of a larger n, per lane); the per-slice budget table of HQ_CBR / LD pictures is not the one the context
  *     holds (first sight, or a change of y_slices, x_slices, compressed_bytes, scalar or prefix: a context that alternates
  *     HQ_CBR and LD pictures, or two budgets, uploads and waits at every change); the whole-plane inverse transform meets
- *     another (wavelet, depth) than the one before.  Otherwise it allocates nothing, copies nothing to or from the host and
- *     waits for nothing.  vc2hip_sync and vc2hip_set_streams always wait.
+ *     another quantisation matrix than the one before (another wavelet or depth, or vc2hip_set_quant_matrix).  Otherwise it
+ *     allocates nothing, copies nothing to or from the host and waits for nothing.  vc2hip_sync and vc2hip_set_streams always
+ *     wait.
  *   - graph capture: warm the context up first -- one eager call of every captured call, with the same fmt, cp and n, and
  *     a vc2hip_sync -- so that none of the waits above falls inside the capture (there it fails: VC2HIP_EHIP, and the
  *     capture is invalid).  A captured call returns VC2HIP_OK and leaves the context's host-side state as it was.  Errors
@@ -400,6 +403,37 @@ int vc2hip_set_packed_format(vc2hip_ctx *ctx, const vc2hip_packed_format *pf); /
 /* Host arithmetic: bytes from a picture's base to the end of its furthest row under pf; 0 for what the calls refuse for
  * pictures of fmt (a NULL pf or packing NONE included: that is no packed format). */
 size_t vc2hip_packed_picture_bytes(const vc2hip_picture_format *fmt, const vc2hip_packed_format *pf);
+/* The context's quantisation matrix: what every band's index is lowered by, max(q - matrix[band], 0), in place of the default
+ * matrix of the wavelet and depth (vc2hip_quant_matrix).  SMPTE 2042-1 lets every picture carry its own (custom_quant_matrix in
+ * the transform parameters); encoders use that for flat matrices, perceptual weighting, or depths whose default they do not
+ * want.  The reference's Library functions take any matrix, its stream layer refuses the flag (DataUnit.cpp:1403-1405).
+ *   matrix   3 * depth + 1 entries in the order of vc2hip_quant_matrix: LL, then per level from the coarsest HL, LH, HH.
+ *            Entries 0 ... 255; an entry above 119 means "never quantise this band" for every index a slice can carry.
+ *            NULL: the default matrix of each call's wavelet and depth again (depth is not looked at)
+ * While a matrix is set, EVERY call of the context that takes a vc2hip_coding_params uses it in place of the default: the
+ * host-buffer picture calls, the _begin / _end calls, vc2hip_encode_batch_dev in all four modes, vc2hip_decode_batch_dev (HQ and
+ * LD), vc2hip_decode_reduced_batch_dev (the entries of the levels it keeps), vc2hip_encode_recon_batch_dev, the two fields
+ * calls, both transcoders (input and output alike) and the stream calls below (the writers put it into every picture, the
+ * reader asks it of every picture).  Results are byte for byte those of the reference's Library functions handed that matrix;
+ * the same kernels run, but for the register forms of the slice coder and of the searches, which take entries 0 ... 255 only
+ * where their lane tables can hold the wavelet's band layout -- otherwise the general kernels run, as under the context flags.
+ * VC2HIP_HQ_CAPPED and the capped transcode keep their rule for 115: a band's index max(q - m, 0) never exceeds q, so every
+ * factor used at q <= 115 is one of the monotone ones and a payload's length still never grows with q, whatever the matrix.
+ * The matrix is context state exactly as the sample layout is: the setter launches nothing and waits for nothing, may be called
+ * between any two calls, a captured call keeps the matrix it was captured with (it travels by value in the kernels'
+ * parameters), and the lanes of vc2hip_set_streams and the pictures in flight of the pipelined calls use the context's
+ * matrix at the time of the call.  One wait follows from it: the whole-plane inverse transform (slices beyond any LDS tile)
+ * keeps a device copy of the matrix and uploads it, waiting once, when the matrix in use is not the one it holds.
+ * It does not change: the fine-grained int32 calls (they take their own qmatrix argument), vc2hip_quant_matrix,
+ * vc2hip_picture_header, and the command-line tools (which never set one).
+ * VC2HIP_EINVAL -- from the setter for an entry outside 0 ... 255 or a depth outside 1 ... 7, and the context keeps the matrix
+ * it had; from every call above whose cp->depth is not the matrix's depth: nothing is launched and no output byte is touched.
+ * Not provided: an option of the command-line tools; DecodeStream on streams that carry a matrix; a matrix per picture within
+ * one batch call; asymmetric transforms.  At the stream level an extension (the reference refuses the flag), below it parity. */
+int vc2hip_set_quant_matrix(vc2hip_ctx *ctx, const int32_t *matrix, int depth);
+/* Copies up to cap entries of the matrix the context holds into out (which may be null when cap is 0) and returns the number
+ * held: 3 * depth + 1, or 0 while none is set (VC2HIP_EINVAL for a null context). */
+int vc2hip_get_quant_matrix(const vc2hip_ctx *ctx, int32_t *out, int cap);
 int vc2hip_encode_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
                             const vc2hip_picture_format *fmt, const vc2hip_coding_params *cp,
                             void *d_payload, size_t payload_stride, uint64_t *d_lens);
@@ -503,8 +537,9 @@ int vc2hip_decode_fields_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_
  * Per picture i, from slot[:min(d_lens_in[i], payload_stride_in)] and an index q_i:
  *   1. the slices are read as vc2hip_decode_batch_dev reads them: quantised coefficients and every slice's own index q_s;
  *   2. slice s ends at q'_s = max(q_s, q_i).  A slice with q'_s == q_s keeps its coefficient values: no arithmetic is done on
- *      them.  Every other coefficient c becomes quant(scale(c, q_s), q'_s) (Quantisation.cpp:69-95) with the default
- *      quantisation matrix of cp's wavelet and depth, per band max(q - matrix[band], 0) as everywhere;
+ *      them.  Every other coefficient c becomes quant(scale(c, q_s), q'_s) (Quantisation.cpp:69-95) with the context's
+ *      matrix (vc2hip_set_quant_matrix; the default of cp's wavelet and depth while none is set) for the input and the output
+ *      alike, per band max(q - matrix[band], 0) as everywhere;
  *   3. the result is written as vc2hip_hq_pack writes VBR slices: trailing zeros trimmed, each component rounded up to the
  *      scalar.  Always a plain HQ VBR payload at cp's prefix and scalar, never finer than the input; HQ_CBR input loses its
  *      padding.  |c'| <= |c| everywhere and the length never grows with q_i.
@@ -533,7 +568,7 @@ int vc2hip_decode_fields_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size_
  * min(d_lens_in[i], payload_stride_in) is read; the bytes of an output slot past d_lens_out[i] are unspecified.  Pictures whose
  * decoded values leave the encoder's domain (|c| > 65534, an index of 116 .. 119) are held to those memory and isolation
  * rules only.
- * Not provided: LD, custom quantisation matrices, an option of the command-line tools (a per-slice budget and a change of
+ * Not provided: LD, an option of the command-line tools (a per-slice budget and a change of
  * prefix or scalar: vc2hip_transcode_cbr_batch_dev below).  Extension, no counterpart in the reference. */
 typedef struct {
   int q_index;    /* the target: every slice ends at max(its own index, q_i); 0 .. VC2HIP_CAP_Q_TOP */
@@ -558,8 +593,8 @@ int vc2hip_transcode_batch_dev(vc2hip_ctx *ctx,
  *      KEPT iff every component's length byte is at most 255 and need_s <= B[s] - 4;
  *   3. a kept slice ends at q'_s = q_s with its values untouched: no arithmetic is done on them;
  *   4. every other slice is SEARCHED: C = scale(c, q_s), q'_s = what the HQ_CBR encoder's search (quantIndicesCBR,
- *      EncodeStream.cpp:73-125) finds for the slice on C under B[s] and cp_out's scalar, its values quant(C, q'_s); default
- *      quantisation matrix, per band max(q - matrix[band], 0) as everywhere;
+ *      EncodeStream.cpp:73-125) finds for the slice on C under B[s] and cp_out's scalar, its values quant(C, q'_s); the
+ *      context's matrix (vc2hip_set_quant_matrix) for input and output alike, per band max(q - matrix[band], 0) as everywhere;
  *   5. the result is written as vc2hip_hq_pack writes HQ_CBR slices at cp_out's prefix and scalar: every picture is
  *      sum(B) + slices * prefix bytes, which is d_lens_out[i].
  * The keep rule makes the call stable across generations: its output fed to it again under the same cp_out comes back byte
@@ -579,8 +614,7 @@ int vc2hip_transcode_batch_dev(vc2hip_ctx *ctx,
  * search trial whose adjusted index passes 119), VC2HIP_ESCALAR (a search trial), VC2HIP_ECBR_TOOBIG / VC2HIP_ECBR_LEN (the
  * CBR writer: e.g. a roomy budget whose V padding passes 255 * scalar).  Memory and isolation rules, and the pictures
  * outside the encoder's domain, as for the call above.
- * Not provided: LD, custom quantisation matrices, an option of the command-line tools.  Extension, no counterpart in the
- * reference. */
+ * Not provided: LD, an option of the command-line tools.  Extension, no counterpart in the reference. */
 int vc2hip_transcode_cbr_batch_dev(vc2hip_ctx *ctx,
         const void *d_payload_in, size_t payload_stride_in, const uint64_t *d_lens_in, int n,
         const vc2hip_picture_format *fmt,
@@ -615,9 +649,33 @@ typedef struct {
  * VC2HIP_ECAP, when they exceed cap). */
 int vc2hip_picture_header(const vc2hip_coding_params *cp, int major_version, uint32_t picture_number,
                           uint8_t *out, size_t cap, size_t *len);
+/* Host only: vc2hip_picture_header with a quantisation matrix of the picture's own.  matrix != NULL (3 * depth + 1 entries in the
+ * order of vc2hip_quant_matrix, depth == cp->depth, 1 ... 7, entries 0 ... 255; VC2HIP_EINVAL otherwise): the
+ * custom_quant_matrix flag is 1, the entries follow as unsigned interleaved exp-Golomb codes, zero bits pad to the byte
+ * boundary.  matrix == NULL: vc2hip_picture_header's bytes (depth is not looked at).  At most 85 bytes. */
+int vc2hip_picture_header_qm(const vc2hip_coding_params *cp, int major_version, uint32_t picture_number,
+                             const int32_t *matrix, int depth, uint8_t *out, size_t cap, size_t *len);
+/* Host only, the inverse: the bytes after a picture data unit's parse info (a parameters fragment: its picture number followed
+ * by the bytes behind its 8-byte fragment header) -> kernel, depth, slice counts and, HQ (is_ld 0), prefix and scalar with mode
+ * VC2HIP_HQ_CONSTQ, or, LD, mode VC2HIP_LD and compressed_bytes = fraction * slices.  The other members of *cp_out are 0.
+ * *entries_out = the picture's matrix entries, 0 when custom_quant_matrix is clear; the first matrix_cap of them are written
+ * to matrix_out (VC2HIP_ECAP when there are more; matrix_out may be null when matrix_cap is 0).  *consumed (may be null) = the
+ * header's bytes: the slice data starts there.  This is how a caller learns what to hand vc2hip_set_quant_matrix and the
+ * stream reader from the first picture of a stream it did not write.
+ * VC2HIP_ESYNTAX: the header runs past len; an asymmetric transform other than the identity; a matrix entry above 255; a matrix
+ * at a depth above 7; a wavelet index above 6; a depth above 30; an LD fraction that is no whole number of bytes a picture; a
+ * slice count, prefix, scalar or LD numerator / denominator of 2^31 or more, which the ints of *cp_out cannot hold.  In that last
+ * point the function is stricter than vc2hip_stream_read_dev, which compares the 32-bit fields with the caller's cp (whose ints
+ * they cannot equal) and takes an LD fraction in any terms.  VC2HIP_EINVAL: null bytes, cp_out or entries_out,
+ * major_version < 1. */
+int vc2hip_parse_picture_header(const uint8_t *bytes, size_t len, int major_version, int is_ld, vc2hip_coding_params *cp_out,
+                                int32_t *matrix_out, int matrix_cap, int *entries_out, size_t *consumed);
 /* Slots -> n picture data units (HQ or LD by cp->mode) at d_stream, then the end of sequence if asked for.  next / prev
  * parse offsets are chained from sp->prev_parse_offset on.  *d_stream_len (device) = the bytes the units need, even past
- * cap; nothing is written at or past cap (VC2HIP_ECAP at sync).  d_stream must be 16-byte aligned. */
+ * cap; nothing is written at or past cap (VC2HIP_ECAP at sync).  d_stream must be 16-byte aligned.
+ * While the context holds a matrix (vc2hip_set_quant_matrix) every picture's header is vc2hip_picture_header_qm's with it --
+ * also when it equals the default: set means written; cp->depth must be the matrix's depth (VC2HIP_EINVAL).  Stream bytes:
+ * sum of lens + n * (13 + the header's length) + 13 for the end of sequence, the header's length being that function's *len. */
 int vc2hip_stream_write_dev(vc2hip_ctx *ctx, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
                             const vc2hip_coding_params *cp, const vc2hip_stream_params *sp,
                             uint8_t *d_stream, size_t cap, uint64_t *d_stream_len);
@@ -626,7 +684,8 @@ int vc2hip_stream_write_dev(vc2hip_ctx *ctx, const void *d_payload, size_t paylo
  * Picture k, in order, is
  *   the parameters fragment: parse info (code 0xEC HQ, 0xCC LD), picture number first_picture_number + k (mod 2^32, 4 bytes),
  *       fragment data length (2 bytes: the length of the transform parameters), slice count 0 (2 bytes), the transform
- *       parameters -- the bytes of vc2hip_picture_header after its first four, at sp->major_version;
+ *       parameters -- the bytes of vc2hip_picture_header after its first four, at sp->major_version; while the context holds a
+ *       matrix (vc2hip_set_quant_matrix), those of vc2hip_picture_header_qm with it, in every picture's parameters fragment;
  *   slice fragments: parse info, picture number (4), data length (2), slice count (2), slice offset x (2) and y (2), then
  *       that many whole slices in raster order.
  * Grouping is the reference's greedy rule: a slice starts a new fragment when the current one holds at least one slice and
@@ -643,7 +702,7 @@ int vc2hip_stream_write_dev(vc2hip_ctx *ctx, const void *d_payload, size_t paylo
  *       fragments to a network stack without parsing the stream again.
  * Worst case, to allocate by: at most y_slices * x_slices + 1 units per picture, plus one for the end of sequence; stream
  * bytes at most sum of lens + n * (21 + parameter bytes) + n * y_slices * x_slices * 25 + 13 (the parameter bytes are
- * vc2hip_picture_header's length - 4).
+ * the header's length - 4: vc2hip_picture_header's, or with a matrix set vc2hip_picture_header_qm's, at most 81).
  * VC2HIP_EINVAL, nothing launched, no output byte touched: sp->major_version < 3 (fragments exist from version 3 on, as
  * DataUnit.cpp:1065-1067 forces it); fragment_length outside 1 ... 65535; x_slices or y_slices above 65535, or more than
  * 2^24 slices; the unit-table arguments not all given or all absent; d_stream or the slots not 16-byte aligned, the other
@@ -666,9 +725,16 @@ int vc2hip_stream_write_fragments_dev(vc2hip_ctx *ctx, const void *d_payload, si
 /* The first n pictures of a stream (len bytes at d_stream, any alignment) -> slots + lens, plus each picture's number and the
  * bytes consumed up to the end of the n-th picture (either may be NULL; a second call can resume at d_stream + consumed).
  * Sequence headers give the major version; padding and auxiliary units are skipped; whole pictures and fragmented pictures
- * (HQ and LD) are read.  Every picture's parameters must be those of cp.  VC2HIP_ESYNTAX at sync: a bad parse-info prefix,
+ * (HQ and LD) are read.  Every picture's parameters must be those of cp, and its EFFECTIVE quantisation matrix -- its own
+ * where custom_quant_matrix is set (parsed on the device), else the default of its wavelet and depth -- must equal the
+ * context's effective matrix entry by entry: the one vc2hip_set_quant_matrix set, else the default.  So a stream that carries
+ * the default matrix explicitly is read by a context with none set, and a context set to the default reads streams without
+ * one.  VC2HIP_ESYNTAX at sync, with the byte offset of the unit: a bad parse-info prefix,
  * an unknown parse code, a unit past len, a picture whose next_parse_offset is 0, fewer than n pictures, parameters that
- * differ from cp, a custom quantisation matrix, an asymmetric transform other than the identity, fragments out of order. */
+ * differ from cp, a quantisation matrix that differs from the context's, a matrix entry above 255 (the text names the limit),
+ * an asymmetric transform other than the identity, fragments out of order.  A unit head longer than the 128 bytes the walk
+ * looks at counts as running past the end; the longest head the call accepts (a parameters fragment with 22 entries) has 103.
+ * VC2HIP_EINVAL, nothing launched: cp->depth is not the depth of the context's matrix. */
 int vc2hip_stream_read_dev(vc2hip_ctx *ctx, const uint8_t *d_stream, size_t len, int n,
                            const vc2hip_coding_params *cp, const vc2hip_stream_params *sp,
                            void *d_payload, size_t payload_stride, uint64_t *d_lens,

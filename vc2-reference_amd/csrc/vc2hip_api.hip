@@ -132,7 +132,7 @@ enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS,
        B_INDEX, B_PLANE, B_PLANE2, B_CBRB, B_CBRO, B_QM, B_UNITS, B_SEGS,
        B_FRAGS, B_FRAGPIC, B_FRAGJUMP, // stream_write_fragments_dev: fragment tables, per-picture results, the cut's workspace
        B_RSTORE, B_RSTOREW, // encode_recon_batch_dev: the quantised coefficients in the decoder's layout
-       B_PLANE_QM,          // plane_inverse: the quantisation matrix of plane_qm_key
+       B_PLANE_QM,          // plane_inverse: the device copy of the quantisation matrix in plane_qm_held
        B_CAPTAB,            // HQ_CAPPED: the per-picture length table (vc2hip_cap.h)
        B_PKIN, B_PKOUT,     // vc2hip_set_packed_format: the planar staging of a call's input and of its output pictures
        B_TCLEN, B_TCQ,      // vc2hip_transcode_batch_dev: the indices handed to the slice coder, the pictures' indices of the capped form
@@ -156,7 +156,8 @@ struct vc2hip_ctx {
   // cached CBR / LD slice-size tables (re-uploaded only when the parameters change)
   int cbr_key[2][5] = {{-1, -1, -1, -1, -1}, {-1, -1, -1, -1, -1}}; // (two slots: budget_tables)
   uint64_t cbr_total[2] = {0, 0};
-  int plane_qm_key[2] = {-1, -1}; // (kernel, depth) of the quantisation matrix in B_PLANE_QM (whole-plane inverse path)
+  int32_t plane_qm_held[VC2_MAX_BANDS] = {}; // the quantisation matrix in B_PLANE_QM (whole-plane inverse path), entry by entry
+  int plane_qm_n = 0;                        // ... and how many entries of it (0: none uploaded yet)
   int debug_skip = 0;
   // VBR payload assembly.  Default: fixed-stride slots + scan + compaction (three launches).
   // VC2HIP_SINGLE_PASS_VBR=1: decoupled look-back inside the pack kernel -- measured 2x SLOWER on
@@ -225,6 +226,10 @@ struct vc2hip_ctx {
   // vc2hip_set_packed_format: v210 or semi-planar pictures (pure host state as the layout; while set the layout is not used)
   vc2hip_packed_format packed = {};
   bool has_packed = false;
+  // vc2hip_set_quant_matrix: the quantisation matrix of every call that takes a vc2hip_coding_params (pure host state as the
+  // layout; qm_depth 0: none set, every call uses the default matrix of its wavelet and depth -- effective_matrix)
+  int32_t qm[VC2_MAX_BANDS] = {};
+  int qm_depth = 0;
 };
 
 static const char *code_text(int code) {
@@ -463,9 +468,10 @@ static int err_from_flags(vc2hip_ctx *c, unsigned f) {
                                              "data unit runs past the end of the stream", "next_parse_offset is 0",
                                              "end of sequence before the pictures asked for",
                                              "picture parameters differ from the coding parameters",
-                                             "custom quantisation matrix flag set", "asymmetric transform",
+                                             "quantisation matrix differs from the context's", "asymmetric transform",
                                              "picture before any sequence header and no major version given",
-                                             "fragment out of order", "?"};
+                                             "fragment out of order", "?",
+                                             "quantisation matrix entry above 255, the largest the library takes"};
     const unsigned w = *(const unsigned *)((const char *)c->h_err + VC2_ERRBLK_SYNTAX_WHY);
     char b[256];
     if (w == VC2_SYN_SLICE_TOO_LONG) {
@@ -533,6 +539,7 @@ extern "C" int vc2hip_set_streams(vc2hip_ctx *c, int k) {
 
 // One caller buffer of a device batch call.  An item is a picture, or a frame for the two field calls: a frame takes two
 // payload slots and two lengths, and that factor of two is in `each` and nowhere else.
+static void inherit_matrix(vc2hip_ctx *child, const vc2hip_ctx *c); // (vc2hip_set_quant_matrix, below)
 struct BatchBuf {
   const void *p; // null where the call allows it: it has no range then, and a lane's pointer stays null
   size_t each;   // bytes per item
@@ -589,6 +596,7 @@ template <size_t NB, class F> static int split_batch(vc2hip_ctx *c, int n, const
     c->in_split = (i == 0);
     l->layout = c->layout; l->has_layout = c->has_layout; // (host state: a lane's pictures lie as the context's)
     l->packed = c->packed; l->has_packed = c->has_packed;
+    if (l != c) inherit_matrix(l, c);
     void *at[NB];
     for (size_t b = 0; b < NB; ++b) at[b] = bufs[b].p ? (uint8_t *)bufs[b].p + (size_t)first[i] * bufs[b].each : nullptr;
     const int r = fn(l, count[i], at);
@@ -917,6 +925,46 @@ struct LayoutBypass { // a host-buffer picture call: its pictures are in the fil
   explicit LayoutBypass(vc2hip_ctx *ctx) : c(ctx), was(ctx->layout_bypass) { c->layout_bypass = true; }
   ~LayoutBypass() { c->layout_bypass = was; }
 };
+
+// ---- the context's quantisation matrix (vc2hip_set_quant_matrix) ----------------------------------
+// Host state only.  Every kernel takes its matrix by value in its parameters (the qmatrix member of the params structs), so
+// a captured call keeps the one it was captured with; the one device-side copy, plane_inverse's, is keyed by its entries.
+extern "C" int vc2hip_set_quant_matrix(vc2hip_ctx *c, const int32_t *m, int depth) {
+  if (!c) return VC2HIP_EINVAL;
+  if (!m) { c->qm_depth = 0; return VC2HIP_OK; }
+  if (depth < 1 || depth > VC2_MAX_DEPTH) return set_err(c, VC2HIP_EINVAL, "set_quant_matrix: depth must be 1 ... 7");
+  for (int b = 0; b < 3 * depth + 1; ++b)
+    if (m[b] < 0 || m[b] > 255) return set_err(c, VC2HIP_EINVAL, "set_quant_matrix: every entry must be 0 ... 255");
+  memcpy(c->qm, m, (size_t)(3 * depth + 1) * 4);
+  c->qm_depth = depth;
+  return VC2HIP_OK;
+}
+extern "C" int vc2hip_get_quant_matrix(const vc2hip_ctx *c, int32_t *out, int cap) {
+  if (!c || cap < 0 || (cap && !out)) return VC2HIP_EINVAL;
+  const int n = c->qm_depth ? 3 * c->qm_depth + 1 : 0;
+  for (int b = 0; b < n && b < cap; ++b) out[b] = c->qm[b];
+  return n;
+}
+// The one owner: the matrix a call of context c with coding parameters cp quantises by -- the context's while one is set
+// (cp->depth must be its depth), else the default of cp's wavelet and depth.  qm: VC2_MAX_BANDS entries.  Its refusal is
+// matrix_depth_check, which the entry points make before they launch anything (batch_args, the fronts of the picture and
+// stream calls); a context with no matrix set is refused nothing it was not refused before.
+static int matrix_depth_check(vc2hip_ctx *c, const vc2hip_coding_params *cp) {
+  if (c->qm_depth && cp->depth != c->qm_depth)
+    return set_err(c, VC2HIP_EINVAL, "the context's quantisation matrix is for another transform depth than cp->depth");
+  return VC2HIP_OK;
+}
+static int effective_matrix(vc2hip_ctx *c, const vc2hip_coding_params *cp, int32_t *qm) {
+  if (int rc = matrix_depth_check(c, cp)) return rc;
+  if (c->qm_depth) { memcpy(qm, c->qm, (size_t)(3 * c->qm_depth + 1) * 4); return VC2HIP_OK; }
+  const int rc = cp->depth > VC2_MAX_DEPTH ? VC2HIP_EINVAL : vc2hip_quant_matrix(cp->kernel, cp->depth, qm);
+  return rc ? set_err(c, rc) : VC2HIP_OK;
+}
+// a child context (a vc2hip_set_streams lane, a picture in flight) codes with its parent's matrix at the time of the call
+static void inherit_matrix(vc2hip_ctx *child, const vc2hip_ctx *c) {
+  child->qm_depth = c->qm_depth;
+  memcpy(child->qm, c->qm, sizeof c->qm);
+}
 
 static size_t max_slice_bytes(int prefix, int scalar) { return (size_t)prefix + 4 + 3 * 255 * (size_t)scalar; }
 extern "C" size_t vc2hip_max_payload_bytes(const vc2hip_picture_format *f, const vc2hip_coding_params *cp) {
@@ -1285,15 +1333,16 @@ static int plane_inverse(vc2hip_ctx *c, const Geom &g, int kernel, int n, const 
   int *d_qm;
   NEED(c, B_PLANE, plane_elems(g) * n * 4, d_plane);
   NEED(c, B_PLANE_QM, 256, d_qm);
-  // the matrix follows from (kernel, depth): uploaded when they change, as the CBR / LD budget tables are -- no copy and no
-  // wait in any later call.  (A reduced picture's matrix is the first 3 (depth - drop) + 1 entries of the CODED picture's:
-  // the key carries that depth, g.depth + level_base, beside the depth of the entries in use.)
-  const int key[2] = {kernel, g.depth | (g.depth + level_base) << 8};
-  if (memcmp(key, c->plane_qm_key, sizeof key)) {
-    c->plane_qm_key[0] = -1;
-    HIPCHK(c, hipMemcpyAsync(d_qm, qm, (size_t)(3 * g.depth + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  // the device copy is keyed by the matrix itself (a context's matrix is the caller's to change: vc2hip_set_quant_matrix):
+  // uploaded when an entry in use differs, as the CBR / LD budget tables are -- no copy and no wait in any later call.  (A
+  // reduced picture uses the first 3 (depth - drop) + 1 entries of the CODED picture's matrix: those are what is compared.)
+  const int nb = 3 * g.depth + 1;
+  if (nb != c->plane_qm_n || memcmp(qm, c->plane_qm_held, (size_t)nb * 4)) {
+    c->plane_qm_n = 0;
+    HIPCHK(c, hipMemcpyAsync(d_qm, qm, (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // qm lives on the caller's stack
-    memcpy(c->plane_qm_key, key, sizeof key);
+    memcpy(c->plane_qm_held, qm, (size_t)nb * 4);
+    c->plane_qm_n = nb;
   }
   const int ns = g.ys * g.xs;
   size_t off = 0;
@@ -2128,7 +2177,7 @@ static int batch_args(vc2hip_ctx *c, int n, const vc2hip_picture_format *f, cons
   if (missing) return set_err(c, VC2HIP_EINVAL, null_text);
   if (misaligned) return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
   if (cp->kernel < 0 || cp->kernel > 6) return set_err(c, VC2HIP_EINVAL, "invalid wavelet kernel");
-  return VC2HIP_OK;
+  return matrix_depth_check(c, cp);
 }
 // what the three encoding calls refuse in cp; g: the coded picture's geometry
 static int encode_check(vc2hip_ctx *c, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, Geom &g) {
@@ -2199,7 +2248,7 @@ static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, 
   int rc;
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
-  if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
+  if ((rc = effective_matrix(c, cp, qm))) return rc;
   const bool s16 = cp->mode != VC2HIP_LD && use_store16(c, g, cp->kernel);
   int32_t *d_store, *d_ll, *d_q, *d_storew = nullptr, *d_llw = nullptr;
   NEED(c, B_STORE, (size_t)n * ns * g.slice_coefs * 4, d_store); // 16-bit elements use the first half
@@ -2439,7 +2488,7 @@ static int decode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_paylo
   int rc;
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
-  if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
+  if ((rc = effective_matrix(c, cp, qm))) return rc;
   const int norm_shift = drop * (cp->kernel == VC2HIP_HAAR0 ? 0 : cp->kernel == VC2HIP_FIDELITY ? 2 : 1);
   const bool s16 = !ld && use_store16(c, g, cp->kernel);
   const void *dstc[3]; RawPlane ds[3];
@@ -2561,9 +2610,13 @@ void stream_ab(const vc2hip_coding_params *cp, uint32_t *a, uint32_t *b) {
 }
 } // namespace
 
-extern "C" int vc2hip_picture_header(const vc2hip_coding_params *cp, int major_version, uint32_t picture_number, uint8_t *out,
-                                     size_t cap, size_t *len) {
+extern "C" int vc2hip_picture_header_qm(const vc2hip_coding_params *cp, int major_version, uint32_t picture_number,
+                                        const int32_t *matrix, int depth, uint8_t *out, size_t cap, size_t *len) {
   if (!stream_cp_ok(cp) || major_version < 1 || !len || (cap && !out)) return VC2HIP_EINVAL;
+  if (matrix) {
+    if (depth != cp->depth || depth < 1 || depth > VC2_MAX_DEPTH) return VC2HIP_EINVAL;
+    for (int i = 0; i < 3 * depth + 1; ++i) if (matrix[i] < 0 || matrix[i] > 255) return VC2HIP_EINVAL;
+  }
   uint32_t a, b;
   stream_ab(cp, &a, &b);
   HeaderBits w{out, cap};
@@ -2575,10 +2628,71 @@ extern "C" int vc2hip_picture_header(const vc2hip_coding_params *cp, int major_v
   w.uvlc((uint32_t)cp->y_slices);
   w.uvlc(a);
   w.uvlc(b);
-  w.bit(0); // custom quantisation matrix
+  w.bit(matrix ? 1 : 0); // custom_quant_matrix, then its entries: LL, then HL, LH, HH per level from the coarsest (DataUnit.cpp:1403)
+  if (matrix) for (int i = 0; i < 3 * depth + 1; ++i) w.uvlc((uint32_t)matrix[i]);
   w.align();
   *len = w.pos;
   return w.pos > cap ? VC2HIP_ECAP : VC2HIP_OK;
+}
+extern "C" int vc2hip_picture_header(const vc2hip_coding_params *cp, int major_version, uint32_t picture_number, uint8_t *out,
+                                     size_t cap, size_t *len) {
+  return vc2hip_picture_header_qm(cp, major_version, picture_number, nullptr, 0, out, cap, len);
+}
+
+// The inverse of vc2hip_picture_header_qm on the host: the bit syntax k_stream_walk reads (vc2hip_stream.hip).  The two differ
+// in what they do with the values: the walk compares 32-bit fields with the caller's cp and takes an LD fraction in any terms;
+// this function has to return them in a vc2hip_coding_params, whose members are ints, so a slice count, prefix, scalar or LD
+// numerator / denominator of 2^31 or more is VC2HIP_ESYNTAX here (include/vc2hip.h says so).
+extern "C" int vc2hip_parse_picture_header(const uint8_t *bytes, size_t len, int major_version, int is_ld, vc2hip_coding_params *cp_out,
+                                           int32_t *matrix_out, int matrix_cap, int *entries_out, size_t *consumed) {
+  if (!bytes || !cp_out || !entries_out || major_version < 1 || matrix_cap < 0 || (matrix_cap && !matrix_out)) return VC2HIP_EINVAL;
+  size_t pos = 32; // bits; the picture number
+  bool over = len < 4;
+  auto bit = [&]() -> unsigned {
+    if ((pos >> 3) >= len) { over = true; return 1; } // (ones past the end: every code below ends)
+    const unsigned v = bytes[pos >> 3] >> (7 - (pos & 7)) & 1;
+    ++pos;
+    return v;
+  };
+  auto uvlc = [&]() -> uint32_t {
+    unsigned long long v = 1;
+    for (int n = 0; !bit(); ++n) {
+      if (n == 32) { over = true; break; }
+      v = (v << 1) | bit();
+    }
+    return (uint32_t)(v - 1);
+  };
+  const uint32_t kernel = uvlc(), depth = uvlc();
+  bool asym = false;
+  if (major_version >= 3) {
+    if (bit()) asym |= uvlc() != kernel; // asym_transform_index_flag: wavelet_index_ho
+    if (bit()) asym |= uvlc() != 0;      // asym_transform_flag: dwt_depth_ho
+  }
+  const uint32_t xs = uvlc(), ys = uvlc(), a = uvlc(), b = uvlc();
+  const bool custom = bit() && !over;
+  if (over || asym || kernel > 6 || depth > 30 || (xs | ys | a | b) >> 31) return VC2HIP_ESYNTAX;
+  int entries = 0;
+  if (custom) {
+    if (depth > VC2_MAX_DEPTH) return VC2HIP_ESYNTAX;
+    entries = 3 * (int)depth + 1;
+    for (int i = 0; i < entries; ++i) {
+      const uint32_t m = uvlc();
+      if (over || m > 255) return VC2HIP_ESYNTAX;
+      if (i < matrix_cap) matrix_out[i] = (int32_t)m;
+    }
+  }
+  memset(cp_out, 0, sizeof *cp_out);
+  cp_out->kernel = (int)kernel; cp_out->depth = (int)depth; cp_out->x_slices = (int)xs; cp_out->y_slices = (int)ys;
+  if (is_ld) { // the slice-bytes fraction a / b: the picture's bytes when b divides a * slices
+    const unsigned long long num = (unsigned long long)a * xs * ys;
+    if (!b || num % b || num / b > 0x7FFFFFFFull) return VC2HIP_ESYNTAX;
+    cp_out->mode = VC2HIP_LD; cp_out->compressed_bytes = (int)(num / b);
+  } else {
+    cp_out->mode = VC2HIP_HQ_CONSTQ; cp_out->prefix = (int)a; cp_out->scalar = (int)b;
+  }
+  *entries_out = entries;
+  if (consumed) *consumed = (pos + 7) >> 3;
+  return entries > matrix_cap ? VC2HIP_ECAP : VC2HIP_OK;
 }
 
 extern "C" int vc2hip_stream_write_dev(vc2hip_ctx *c, const void *d_payload, size_t payload_stride, const uint64_t *d_lens, int n,
@@ -2588,10 +2702,12 @@ extern "C" int vc2hip_stream_write_dev(vc2hip_ctx *c, const void *d_payload, siz
   if (((size_t)d_payload | payload_stride | (size_t)d_stream) & 15 || ((size_t)d_lens | (size_t)d_stream_len) & 7)
     return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
   if (sp->major_version < 1) return set_err(c, VC2HIP_EINVAL, "major_version must be at least 1");
+  if (int rc = matrix_depth_check(c, cp)) return rc;
   StreamWriteParams p;
   memset(&p, 0, sizeof p);
-  size_t hl = 0;
-  if (vc2hip_picture_header(cp, sp->major_version, sp->first_picture_number, p.hdr, sizeof p.hdr, &hl))
+  size_t hl = 0; // (a set matrix is written, the default included: set means written)
+  if (vc2hip_picture_header_qm(cp, sp->major_version, sp->first_picture_number, c->qm_depth ? c->qm : nullptr, c->qm_depth, p.hdr,
+                               sizeof p.hdr, &hl))
     return set_err(c, VC2HIP_EINVAL);
   ENTER(c);
   NEED(c, B_UNITS, (size_t)n * 8, p.unit_off);
@@ -2621,11 +2737,13 @@ extern "C" int vc2hip_stream_write_fragments_dev(vc2hip_ctx *c, const void *d_pa
   if (!stream_cp_ok(cp) || cp->x_slices > 65535 || cp->y_slices > 65535 || (long long)cp->x_slices * cp->y_slices > (1 << 24))
     return set_err(c, VC2HIP_EINVAL, "slice counts beyond a fragment's 16-bit slice offsets, or more than 2^24 slices");
   if (payload_stride >= (1ull << 32)) return set_err(c, VC2HIP_EINVAL, "payload_stride must be below 4 GiB");
+  if (int rc = matrix_depth_check(c, cp)) return rc;
   FragParams p;
   memset(&p, 0, sizeof p);
   uint8_t hdr[VC2_STREAM_HDR_MAX];
   size_t hl = 0;
-  if (vc2hip_picture_header(cp, sp->major_version, 0, hdr, sizeof hdr, &hl) || hl < 4) return set_err(c, VC2HIP_EINVAL);
+  if (vc2hip_picture_header_qm(cp, sp->major_version, 0, c->qm_depth ? c->qm : nullptr, c->qm_depth, hdr, sizeof hdr, &hl) || hl < 4)
+    return set_err(c, VC2HIP_EINVAL);
   p.tp_len = (int)hl - 4; // the transform parameters: the header without its picture number
   memcpy(p.tp, hdr + 4, (size_t)p.tp_len);
   ENTER(c);
@@ -2669,9 +2787,21 @@ extern "C" int vc2hip_stream_read_dev(vc2hip_ctx *c, const uint8_t *d_stream, si
   if (((size_t)d_payload | payload_stride) & 15 || ((size_t)d_lens | (size_t)d_consumed) & 7 || (size_t)d_picture_numbers & 3)
     return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
   if (!stream_cp_ok(cp) || sp->major_version < 0 || payload_stride >= (1ull << 32)) return set_err(c, VC2HIP_EINVAL);
-  ENTER(c);
+  if (int rc = matrix_depth_check(c, cp)) return rc;
   StreamReadParams p;
   memset(&p, 0, sizeof p);
+  // The context's effective matrix, against which the walk holds every picture's: its own entries, or -- custom_quant_matrix
+  // clear -- the default of its wavelet and depth, which are cp's by then (flagless_ok says whether that default is ours).
+  // Beyond depth 7 there is no matrix to set or to compare: pictures without one pass, pictures with one are refused.
+  if (cp->depth <= VC2_MAX_DEPTH) {
+    int32_t qm[VC2_MAX_BANDS], dflt[VC2_MAX_BANDS];
+    if (int rc = effective_matrix(c, cp, qm)) return rc;
+    if (vc2hip_quant_matrix(cp->kernel, cp->depth, dflt)) return set_err(c, VC2HIP_EINVAL);
+    p.qm_entries = 3 * cp->depth + 1;
+    p.flagless_ok = 1;
+    for (int b = 0; b < p.qm_entries; ++b) { p.qmatrix[b] = qm[b]; p.flagless_ok = p.flagless_ok && qm[b] == dflt[b]; }
+  } else p.flagless_ok = 1;
+  ENTER(c);
   p.seg_cap = cp->y_slices * cp->x_slices + 1; // a picture unit is one segment, a fragment holds at least one slice
   NEED(c, B_SEGS, (size_t)n * p.seg_cap * sizeof(StreamSeg), p.segs);
   NEED(c, B_UNITS, (size_t)n * sizeof(uint2), p.meta);
@@ -2730,7 +2860,7 @@ static int transcode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_in
   int rc;
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
-  if ((rc = vc2hip_quant_matrix(cp->kernel, cp->depth, qm))) return set_err(c, rc);
+  if ((rc = effective_matrix(c, cp, qm))) return rc;
   const bool s16 = use_store16(c, g, cp->kernel);
   const long long sstride = (long long)ns * g.slice_coefs;
   TranscodeParams p;
@@ -2818,7 +2948,7 @@ static int transcode_cbr_batch_common(vc2hip_ctx *c, const Geom &g, const void *
   int rc;
   const int ns = g.ys * g.xs;
   int32_t qm[VC2_MAX_BANDS];
-  if ((rc = vc2hip_quant_matrix(cp_in->kernel, cp_in->depth, qm))) return set_err(c, rc);
+  if ((rc = effective_matrix(c, cp_in, qm))) return rc;
   Budgets out_b;
   if ((rc = budget_tables(c, g.ys, g.xs, cp_out->compressed_bytes, cp_out->scalar, cp_out->prefix, out_b, nullptr, 1))) return rc;
   if (stride_out < out_b.total) return set_err(c, VC2HIP_ECAP); // (what vc2hip_encode_batch_dev asks under cp_out; before any launch)
@@ -2976,6 +3106,7 @@ extern "C" int vc2hip_encode_picture_hq(vc2hip_ctx *c, const void *raw, const vc
                                         const vc2hip_coding_params *cp, uint8_t *payload, size_t cap, size_t *len,
                                         int32_t *qidx_out) {
   if (!c || !raw || !f || !cp || !payload || !len) return set_err(c, VC2HIP_EINVAL);
+  if (int rc = matrix_depth_check(c, cp)) return rc;
   ENTER(c);
   const size_t rb = vc2hip_raw_picture_bytes(f), pcap = (vc2hip_max_payload_bytes(f, cp) + 15) & ~(size_t)15;
   uint8_t *d_raw, *d_pay; unsigned long long *d_len;
@@ -3007,6 +3138,7 @@ extern "C" int vc2hip_encode_picture_ld(vc2hip_ctx *c, const void *raw, const vc
 static int decode_picture_host(vc2hip_ctx *c, const uint8_t *payload, size_t len, const vc2hip_picture_format *f,
                                const vc2hip_coding_params *cp, void *raw_out, bool ld) {
   if (!c || !payload || !f || !cp || !raw_out) return set_err(c, VC2HIP_EINVAL);
+  if (int rc = matrix_depth_check(c, cp)) return rc;
   ENTER(c);
   const size_t rb = vc2hip_raw_picture_bytes(f);
   const size_t stride = (len + 63) & ~(size_t)63;
@@ -3063,10 +3195,12 @@ extern "C" int vc2hip_encode_picture_begin(vc2hip_ctx *c, const void *raw, const
                                            const vc2hip_coding_params *cp, uint8_t *payload, size_t cap, int32_t *qidx_out,
                                            int *ticket) {
   if (!c || !raw || !f || !cp || !payload) return set_err(c, VC2HIP_EINVAL);
-  vc2hip_ctx::Flight *fl;
-  int rc = flight_begin(c, true, &fl, ticket);
+  int rc = matrix_depth_check(c, cp);
   if (rc) return rc;
+  vc2hip_ctx::Flight *fl;
+  if ((rc = flight_begin(c, true, &fl, ticket))) return rc;
   vc2hip_ctx *l = fl->lane;
+  inherit_matrix(l, c);
   fl->payload = payload; fl->cap = cap;
   const size_t rb = vc2hip_raw_picture_bytes(f), pcap = (vc2hip_max_payload_bytes(f, cp) + 15) & ~(size_t)15;
   uint8_t *d_raw, *d_pay; unsigned long long *d_len;
@@ -3102,10 +3236,12 @@ extern "C" int vc2hip_encode_picture_end(vc2hip_ctx *c, int ticket, size_t *len)
 extern "C" int vc2hip_decode_picture_begin(vc2hip_ctx *c, const uint8_t *payload, size_t len, const vc2hip_picture_format *f,
                                            const vc2hip_coding_params *cp, void *raw_out, int *ticket) {
   if (!c || !payload || !f || !cp || !raw_out) return set_err(c, VC2HIP_EINVAL);
-  vc2hip_ctx::Flight *fl;
-  int rc = flight_begin(c, false, &fl, ticket);
+  int rc = matrix_depth_check(c, cp);
   if (rc) return rc;
+  vc2hip_ctx::Flight *fl;
+  if ((rc = flight_begin(c, false, &fl, ticket))) return rc;
   vc2hip_ctx *l = fl->lane;
+  inherit_matrix(l, c);
   const size_t rb = vc2hip_raw_picture_bytes(f), stride = (len + 63) & ~(size_t)63;
   uint8_t *d_raw, *d_pay; unsigned long long *d_len;
   auto fail = [&](int code) { fl->open = false; return set_err(c, code, l->err.c_str()); };

@@ -40,6 +40,7 @@ enum {
   VC2_SYN_PREFIX = 1, VC2_SYN_CODE, VC2_SYN_PAST_END, VC2_SYN_NEXT_ZERO, VC2_SYN_FEWER, VC2_SYN_PARAMS, VC2_SYN_QUANT_MATRIX,
   VC2_SYN_ASYMMETRIC, VC2_SYN_NO_VERSION, VC2_SYN_FRAGMENT,
   VC2_SYN_SLICE_TOO_LONG, // fragment writer: a slice of more than 65535 bytes (VC2_ERRBLK_SYNTAX_AT holds the picture's index)
+  VC2_SYN_QM_ENTRY,       // a quantisation matrix entry above 255 (VC2_SYN_QUANT_MATRIX: the picture's matrix is not the context's)
   VC2_SYN_COUNT
 };
 
@@ -586,7 +587,11 @@ struct PackedParams {
 void vc2_launch_packed(Launcher &L, const PackedParams &p, bool pack, int n_pictures, hipStream_t s);
 
 // VC-2 stream I/O (vc2hip_stream.hip)
-#define VC2_STREAM_HDR_MAX 48 // picture header bytes the write kernels carry (vc2hip_picture_header is far below it)
+// Picture header bytes the write kernels carry.  The longest vc2hip_picture_header_qm writes: 4 bytes of picture number; wavelet
+// and depth (at most 5 + 7 bits for 0 .. 6 and 0 .. 7 with a matrix); two flags; slice counts, prefix / numerator and scalar /
+// denominator, four codes of at most 63 bits (values below 2^31); the matrix flag; 22 entries of at most 17 bits (0 .. 255):
+// 12 + 2 + 252 + 1 + 374 = 641 bits = 81 bytes, 85 in all.
+#define VC2_STREAM_HDR_MAX 96
 struct StreamWriteParams {
   const uint8_t *payload;           // slots
   long long payload_stride;
@@ -607,7 +612,10 @@ struct StreamReadParams {
   int n, major_version;
   int kernel, depth, ys, xs, ld;    // what every picture must carry
   uint32_t a, b;                    // HQ: prefix, scalar.  LD: the slice-bytes fraction in lowest terms
-  StreamSeg *segs;                  // workspace: n * seg_cap
+  int qmatrix[VC2_MAX_BANDS];       // the context's effective matrix: what a picture's own matrix must equal, entry by entry
+  int qm_entries;                   // 3 * depth + 1; 0: depth beyond 7, a picture with a matrix is refused
+  int flagless_ok;                  // that matrix is the default of (kernel, depth): pictures without a matrix of their own pass
+  StreamSeg *segs;                 // workspace: n * seg_cap
   uint2 *meta;                      // workspace: per picture {segments, payload bytes}
   int seg_cap;
   uint8_t *payload;                 // slots

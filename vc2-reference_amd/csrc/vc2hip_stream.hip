@@ -20,7 +20,13 @@ void vc2_prof_end(Launcher &L, hipStream_t s);
 #define VC2_COPY_THREADS 256
 #define VC2_COPY_WORDS 4 // 16-byte words per thread and chunk
 #define VC2_COPY_CHUNK (VC2_COPY_THREADS * VC2_COPY_WORDS)
-#define VC2_WALK_WINDOW 128 // bytes of a unit the walk looks at: parse info + the longest header it accepts
+// Bytes of a unit the walk looks at: parse info + the longest header it accepts.  That is a parameters fragment with a
+// matrix: 13 bytes of parse info, 8 of fragment header (picture number, data length, slice count), then in bits: wavelet 5
+// (0 .. 6), depth 7 (a matrix comes with depth 1 .. 7), the two asymmetric-transform flags with their values 2 + 5 + 1,
+// the slice counts 2 x 63 (the caller's ints), prefix and scalar or an LD fraction in any terms 2 x 65 (32-bit values),
+// the matrix flag 1, 22 entries of 17 bits (0 .. 255; 256 .. 510 are as long and are named in the refusal): 651 bits = 82
+// bytes, 103 in all.  A longer head runs off the window and is refused as running past the end.
+#define VC2_WALK_WINDOW 128
 
 // bytes [s, s + 16) of the 32 bytes lo:hi (s = 1 .. 15)
 template <int Q> __device__ __forceinline__ uint4 vc2_funnel(const unsigned (&d)[8], unsigned m) {
@@ -479,12 +485,30 @@ __device__ int vc2_check_params(const StreamReadParams &p, Vc2Bits &r, int major
   }
   const uint32_t xs = vc2_uvlc(r), ys = vc2_uvlc(r), a = vc2_uvlc(r), b = vc2_uvlc(r);
   const bool custom_matrix = vc2_bit(r);
-  if (r.bit) { r.bit = 0; ++r.pos; }
   if (r.over) return VC2_SYN_PAST_END;
   if (asym) return VC2_SYN_ASYMMETRIC;
-  if (custom_matrix) return VC2_SYN_QUANT_MATRIX;
   if (ld != (p.ld != 0) || kernel != (uint32_t)p.kernel || depth != (uint32_t)p.depth || xs != (uint32_t)p.xs || ys != (uint32_t)p.ys)
     return VC2_SYN_PARAMS;
+  // The picture's effective matrix against the context's (p.qmatrix): its own 3 * depth + 1 entries (LL, then HL, LH, HH per
+  // level from the coarsest), or the default of its wavelet and depth -- which are the caller's by now, so the host has
+  // compared that one (p.flagless_ok).  Every entry is read before the verdict: an entry above 255 is named as such.
+  if (custom_matrix) {
+    bool differs = p.qm_entries == 0, too_large = false;
+    for (int i = 0; i < 3 * (int)depth + 1 && !too_large; ++i) {
+      uint32_t v = 1; // an entry's code by hand: one of more than 17 bits is an entry above 255 whatever follows, not a walk off the window
+      for (int n = 0; !vc2_bit(r); ++n) {
+        if (n == 9) { too_large = true; break; }
+        v = (v << 1) | vc2_bit(r);
+      }
+      const uint32_t m = v - 1;
+      too_large |= m > 255u;
+      differs |= i >= p.qm_entries || m != (uint32_t)p.qmatrix[i < VC2_MAX_BANDS ? i : 0];
+    }
+    if (r.over) return VC2_SYN_PAST_END;
+    if (too_large) return VC2_SYN_QM_ENTRY;
+    if (differs) return VC2_SYN_QUANT_MATRIX;
+  } else if (!p.flagless_ok) return VC2_SYN_QUANT_MATRIX;
+  if (r.bit) { r.bit = 0; ++r.pos; }
   if (!ld) return a == p.a && b == p.b ? 0 : VC2_SYN_PARAMS;
   return b && (unsigned long long)a * p.b == (unsigned long long)b * p.a ? 0 : VC2_SYN_PARAMS; // the same fraction
 }

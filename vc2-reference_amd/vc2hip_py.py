@@ -98,6 +98,7 @@ EXPORTS = [
     "vc2hip_set_sample_layout", "vc2hip_layout_picture_bytes",
     "vc2hip_set_packed_format", "vc2hip_packed_picture_bytes",
     "vc2hip_transcode_batch_dev", "vc2hip_transcode_cbr_batch_dev",
+    "vc2hip_set_quant_matrix", "vc2hip_get_quant_matrix", "vc2hip_picture_header_qm", "vc2hip_parse_picture_header",
 ]
 
 
@@ -175,6 +176,12 @@ def load_library():
     lib.vc2hip_packed_picture_bytes.restype = C.c_size_t
     lib.vc2hip_picture_header.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, u8p, C.c_size_t,
                                           C.POINTER(C.c_size_t)]
+    lib.vc2hip_picture_header_qm.argtypes = [C.POINTER(CodingParams), C.c_int, C.c_uint32, vp, C.c_int, u8p, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]
+    lib.vc2hip_parse_picture_header.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.POINTER(CodingParams), i32p, C.c_int,
+                                                C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    lib.vc2hip_set_quant_matrix.argtypes = [vp, vp, C.c_int]
+    lib.vc2hip_get_quant_matrix.argtypes = [vp, i32p, C.c_int]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
                                             vp, C.c_size_t, vp]
     lib.vc2hip_stream_write_fragments_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams),
@@ -302,14 +309,44 @@ def stream_params(major_version=2, first_picture_number=0, prev_parse_offset=0, 
     return StreamParams(major_version, first_picture_number & 0xFFFFFFFF, prev_parse_offset, int(end_of_sequence))
 
 
-def picture_header(lib, cp, major_version, picture_number):
-    """vc2hip_picture_header (host only): the bytes after the parse info of an HQ / LD picture data unit"""
-    out = np.zeros(64, np.uint8)
+def _matrix_arg(matrix):
+    """(keep-alive array, pointer, depth) of a quantisation matrix for the C-ABI; None: (None, NULL, 0).  The entries go as
+    they are (what the library refuses is passed on); the depth is what 3 * depth + 1 entries say, 0 for any other count"""
+    if matrix is None:
+        return None, None, 0
+    m = np.ascontiguousarray(matrix, np.int32).ravel()
+    return m, m.ctypes.data_as(C.c_void_p), (m.size - 1) // 3 if m.size % 3 == 1 else 0
+
+
+def picture_header(lib, cp, major_version, picture_number, matrix=None):
+    """vc2hip_picture_header (host only): the bytes after the parse info of an HQ / LD picture data unit; matrix: the
+    picture's own quantisation matrix, 3 * depth + 1 entries (vc2hip_picture_header_qm)"""
+    out = np.zeros(128, np.uint8)
     n = C.c_size_t()
-    rc = lib.vc2hip_picture_header(C.byref(cp), major_version, picture_number & 0xFFFFFFFF, out, out.size, C.byref(n))
+    if matrix is None:
+        rc = lib.vc2hip_picture_header(C.byref(cp), major_version, picture_number & 0xFFFFFFFF, out, out.size, C.byref(n))
+    else:
+        _keep, ptr, depth = _matrix_arg(matrix)
+        rc = lib.vc2hip_picture_header_qm(C.byref(cp), major_version, picture_number & 0xFFFFFFFF, ptr, depth, out, out.size,
+                                          C.byref(n))
     if rc != 0:
         raise Vc2HipError(rc, lib.vc2hip_error_string(rc).decode())
     return out[:n.value].tobytes()
+
+
+def parse_picture_header(lib, data, major_version, ld=False):
+    """vc2hip_parse_picture_header (host only): the bytes after a picture data unit's parse info -> (CodingParams with kernel,
+    depth, slice counts and prefix / scalar or LD's compressed_bytes; the picture's matrix as a list, or None when it carries
+    none; the header's bytes).  Vc2HipError(VC2HIP_ESYNTAX) for what the stream reader refuses in a header."""
+    buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(0, np.uint8)
+    cp = CodingParams()
+    m = np.zeros(22, np.int32)
+    entries, used = C.c_int(), C.c_size_t()
+    rc = lib.vc2hip_parse_picture_header(np.ascontiguousarray(buf), buf.size, major_version, int(ld), C.byref(cp), m, m.size,
+                                         C.byref(entries), C.byref(used))
+    if rc != 0:
+        raise Vc2HipError(rc, lib.vc2hip_error_string(rc).decode())
+    return cp, (m[:entries.value].tolist() if entries.value else None), used.value
 
 
 class Vc2Hip:
@@ -351,7 +388,16 @@ class Vc2Hip:
     def padded_size(self, n, depth):
         return self.lib.vc2hip_padded_size(n, depth)
 
-    def quant_matrix(self, kernel, depth):
+    def quant_matrix(self, kernel=None, depth=None):
+        """quant_matrix(): the matrix the context holds (vc2hip_get_quant_matrix), an empty array while none is set;
+        quant_matrix(kernel, depth): the default matrix of a wavelet and depth (vc2hip_quant_matrix, host only)"""
+        if (kernel is None) != (depth is None):
+            raise TypeError("quant_matrix() takes no argument (the context's matrix) or both kernel and depth (the default matrix)")
+        if kernel is None:
+            out = np.zeros(22, np.int32)
+            n = self.lib.vc2hip_get_quant_matrix(self.h, out, out.size)
+            self._chk(min(n, 0))
+            return out[:n].copy()
         out = np.zeros(3 * depth + 1, np.int32)
         rc = self.lib.vc2hip_quant_matrix(kernel, depth, out)
         if rc:
@@ -541,8 +587,11 @@ class Vc2Hip:
                                                           int(top_field_first), C.byref(cp), d_frames_out))
 
     # ---- VC-2 streams in device memory (the slots + lengths of the batch calls <-> picture data units)
-    def picture_header(self, cp, major_version, picture_number):
-        return picture_header(self.lib, cp, major_version, picture_number)
+    def picture_header(self, cp, major_version, picture_number, matrix=None):
+        return picture_header(self.lib, cp, major_version, picture_number, matrix)
+
+    def parse_picture_header(self, data, major_version, ld=False):
+        return parse_picture_header(self.lib, data, major_version, ld)
 
     def stream_write_dev(self, d_payload, stride, d_lens, n, cp, sp, d_stream, cap, d_stream_len):
         self._chk(self.lib.vc2hip_stream_write_dev(self.h, d_payload, stride, d_lens, n, C.byref(cp), C.byref(sp), d_stream,
@@ -631,6 +680,12 @@ class Vc2Hip:
 
     def packed_picture_bytes(self, fmt, pf):
         return packed_picture_bytes(self.lib, fmt, pf)
+
+    def set_quant_matrix(self, matrix=None):
+        """the quantisation matrix of every call of this context that takes coding parameters, from now on: 3 * depth + 1
+        entries of 0 ... 255 in the order of quant_matrix(kernel, depth); None: the default of each call's wavelet and depth"""
+        _keep, ptr, depth = _matrix_arg(matrix)
+        self._chk(self.lib.vc2hip_set_quant_matrix(self.h, ptr, depth))
 
     def set_streams(self, k):
         self._chk(self.lib.vc2hip_set_streams(self.h, k))

@@ -734,6 +734,12 @@ int vc2hip_stream_write_fragments_dev(vc2hip_ctx *ctx, const void *d_payload, si
  * differ from cp, a quantisation matrix that differs from the context's, a matrix entry above 255 (the text names the limit),
  * an asymmetric transform other than the identity, fragments out of order.  A unit head longer than the 128 bytes the walk
  * looks at counts as running past the end; the longest head the call accepts (a parameters fragment with 22 entries) has 103.
+ * A parameter is compared as the whole number its code holds: one written as the caller's value + 2^32 differs.
+ * Fragments: a picture's fragments follow each other.  Between its parameters fragment and its last slice fragment any other
+ * unit -- padding and auxiliary data too -- is "fragments out of order"; the reference's DecodeStream keeps its fragments by
+ * picture number and takes such units, and other pictures, in between.  A slice fragment's payload is the
+ * fragment_data_length bytes it states (bytes of the unit behind them are skipped); its slice offsets are held against the
+ * running slice count as y * x_slices + x, as the reference places them, so x may exceed a row.
  * VC2HIP_EINVAL, nothing launched: cp->depth is not the depth of the context's matrix. */
 int vc2hip_stream_read_dev(vc2hip_ctx *ctx, const uint8_t *d_stream, size_t len, int n,
                            const vc2hip_coding_params *cp, const vc2hip_stream_params *sp,

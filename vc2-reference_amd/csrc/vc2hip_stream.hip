@@ -461,14 +461,15 @@ __device__ __forceinline__ unsigned vc2_bit(Vc2Bits &r) {
   if (++r.bit == 8) { r.bit = 0; ++r.pos; }
   return v;
 }
-// interleaved exp-Golomb (VLC.cpp:304-317)
-__device__ uint32_t vc2_uvlc(Vc2Bits &r) {
+// interleaved exp-Golomb (VLC.cpp:304-317).  A code of 32 data bits holds 2^32 - 1 ... 2^33 - 2: the value goes back whole, so
+// that a field written as its value + 2^32 differs from the caller's instead of equalling it in 32 bits
+__device__ unsigned long long vc2_uvlc(Vc2Bits &r) {
   unsigned long long v = 1;
   for (int n = 0; !vc2_bit(r); ++n) {
     if (n == 32) { r.over = true; break; }
     v = (v << 1) | vc2_bit(r);
   }
-  return (uint32_t)(v - 1);
+  return v - 1;
 }
 __device__ __forceinline__ uint32_t vc2_be(const unsigned *w, int at, int n) {
   uint32_t v = 0;
@@ -477,13 +478,13 @@ __device__ __forceinline__ uint32_t vc2_be(const unsigned *w, int at, int n) {
 }
 // transform parameters (DataUnit.cpp:1340-1410) against what the caller said the pictures are: 0 or a VC2_SYN_* reason
 __device__ int vc2_check_params(const StreamReadParams &p, Vc2Bits &r, int major, bool ld) {
-  const uint32_t kernel = vc2_uvlc(r), depth = vc2_uvlc(r);
+  const unsigned long long kernel = vc2_uvlc(r), depth = vc2_uvlc(r);
   bool asym = false;
   if (major >= 3) {
     if (vc2_bit(r)) asym |= vc2_uvlc(r) != kernel; // asym_transform_index_flag: wavelet_index_ho
     if (vc2_bit(r)) asym |= vc2_uvlc(r) != 0;      // asym_transform_flag: dwt_depth_ho
   }
-  const uint32_t xs = vc2_uvlc(r), ys = vc2_uvlc(r), a = vc2_uvlc(r), b = vc2_uvlc(r);
+  const unsigned long long xs = vc2_uvlc(r), ys = vc2_uvlc(r), a = vc2_uvlc(r), b = vc2_uvlc(r);
   const bool custom_matrix = vc2_bit(r);
   if (r.over) return VC2_SYN_PAST_END;
   if (asym) return VC2_SYN_ASYMMETRIC;
@@ -510,7 +511,7 @@ __device__ int vc2_check_params(const StreamReadParams &p, Vc2Bits &r, int major
   } else if (!p.flagless_ok) return VC2_SYN_QUANT_MATRIX;
   if (r.bit) { r.bit = 0; ++r.pos; }
   if (!ld) return a == p.a && b == p.b ? 0 : VC2_SYN_PARAMS;
-  return b && (unsigned long long)a * p.b == (unsigned long long)b * p.a ? 0 : VC2_SYN_PARAMS; // the same fraction
+  return b && a * p.b == b * p.a ? 0 : VC2_SYN_PARAMS; // the same fraction (a, b < 2^33 and p.a, p.b < 2^31: no overflow)
 }
 
 // one wavefront: every lane loads two bytes of the unit's window, then every lane parses it (the same bytes from LDS, so the
@@ -548,7 +549,8 @@ __global__ __launch_bounds__(64) void k_stream_walk(StreamReadParams p) {
     else if ((picture || fragment) && major == 0) why = VC2_SYN_NO_VERSION;
     else if (code == 0x00) { // sequence header: its first field is the major version
       Vc2Bits r = {win, 13, uend, 0, false};
-      major = (int)vc2_uvlc(r);
+      const unsigned long long v = vc2_uvlc(r);
+      major = v > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)v;
       if (r.over) why = VC2_SYN_PAST_END;
     } else if (picture) {
       Vc2Bits r = {win, 17, uend, 0, false};

@@ -1862,7 +1862,9 @@ __global__ __launch_bounds__(256) void k_hq_unpack(const UnpackParams p) {
 // round are carried into the next one.  (Rows of 64 make every flush a whole 128-byte line of the store, but the rows of
 // a workgroup then take 37 KB of LDS and three wavefronts per SIMD is all a CU holds; with 32 it holds six.  16 UHD-1 / 32
 // HD / 4 UHD-2 pictures: 0.310 / 0.285 / 0.39 ms with rows of 64, 0.302 / 0.226 / 0.343 ms with rows of 32 and the
-// second request in flight below; rows of 16: 0.32 / 0.215 / 0.37.)
+// second request in flight below; rows of 16: 0.32 / 0.215 / 0.37.)  With byte band planes the rounds behind the record
+// part of a component hold 64 BYTES plus 8 in the same LDS (k_hq_unpack16<true>, "Byte rounds"): 128 UHD pictures 1.58 ->
+// 1.41 ms, VALU instructions per wavefront 9007 -> 7256.
 // ------------------------------------------------------------------------------------------
 // entry: bits [3:0] consumed (1..10), [7:4] coefficients (1..8), [11:8] / [15:12] positions of the two values,
 // [23:16] / [31:24] the values (int8).  No non-zero value: both slots store 0 at position 0 (a zero anyway); one: both
@@ -2251,7 +2253,7 @@ __global__ __launch_bounds__(64 * VC2_UNP16_WAVES) void k_hq_unpack16(const Unpa
   int32_t *wide = p.store_wide + rec0 + (size_t)(active ? slice : 0) * p.slice_coefs;
   const int sy = (active ? slice : 0) / p.xs, sx = (active ? slice : 0) - sy * p.xs;
   // an escape of coefficient j: the wide element with the index of the store element (record or band plane)
-  auto escape = [&](int j, int v) {
+  auto escape = [&](int j, int v) __attribute__((always_inline)) {
     int lw, ow;
     const int at = p.bp.levels ? band_plane_at(p.bp, comp, n, j, sy, sx, lw, ow) : -1;
     if (at >= 0) p.store_wide[(size_t)pic * p.store_stride + (size_t)at] = v;
@@ -2286,8 +2288,23 @@ __global__ __launch_bounds__(64 * VC2_UNP16_WAVES) void k_hq_unpack16(const Unpa
   for (int k = 0; k < UNP_PITCH; k += 8) *(int4 *)(st + k) = make_int4(0, 0, 0, 0);
   __syncthreads(); // the table
   int cnt = 0;     // coefficients of the current round already in the row (carried over from the previous one)
-  for (int base = 0; base < n; base += UNP_N) {
-    const int room = min(UNP_N, n - base);
+  signed char *sb = (signed char *)st; // the row of a byte round (BP8, below): UNB_N + 8 bytes in the same 2 * UNP_PITCH
+  // The long-code path of a byte round: a value that no byte holds goes to the wide array, its byte becomes -128.  The batch
+  // statistic counts PIECES of eight with an escape (choose_bytes8, vc2hip_api.hip): the piece is new if its eight bytes in
+  // the row hold no -128 yet (the bytes from cnt on are still zero).
+  auto byte_of = [&](int j, int v) __attribute__((always_inline)) -> int {
+    if (__builtin_expect((unsigned)(v + 127) <= 254u, 1)) return v;
+    escape(j, v);
+    if (p.stats) {
+      const uint2 pc = *(const uint2 *)(sb + (cnt & ~7));
+      auto has80 = [](unsigned x) -> bool { const unsigned y = x ^ 0x80808080u; return ((y - 0x01010101u) & ~y & 0x80808080u) != 0u; };
+      if (!has80(pc.x) && !has80(pc.y)) atomicAdd(p.stats, 1ull);
+    }
+    return -128;
+  };
+  // The turns of one round: until every lane of the wavefront has `room` coefficients in its row.  bytes: a byte round.
+  auto turns = [&](auto bytes, const int base, const int room) __attribute__((always_inline)) {
+    constexpr bool BY = decltype(bytes)::value;
     for (int turn = 0; cnt < room; ++turn) {
       int used = 0;
       // the look-ups (after two, 13 or more unread bits are left: still a whole index).  Stores go to st[cnt + position]; with no value in the entry they rewrite a zero.
@@ -2303,8 +2320,13 @@ __global__ __launch_bounds__(64 * VC2_UNP16_WAVES) void k_hq_unpack16(const Unpa
         if (e != 0 && (look == 0 || (used != 0 && cnt < room)))
 #endif
         {
-          st[cnt + (int)((e >> 8) & 15u)] = (short)__builtin_amdgcn_sbfe((int)e, 16, 8);
-          st[cnt + (int)((e >> 12) & 15u)] = (short)((int)e >> 24);
+          if constexpr (BY) { // the entry's value bytes as they are
+            sb[cnt + (int)((e >> 8) & 15u)] = (signed char)(e >> 16);
+            sb[cnt + (int)((e >> 12) & 15u)] = (signed char)(e >> 24);
+          } else {
+            st[cnt + (int)((e >> 8) & 15u)] = (short)__builtin_amdgcn_sbfe((int)e, 16, 8);
+            st[cnt + (int)((e >> 12) & 15u)] = (short)((int)e >> 24);
+          }
           cnt += (int)((e >> 4) & 15u);
           used += (int)(e & 15u);
         }
@@ -2320,8 +2342,11 @@ __global__ __launch_bounds__(64 * VC2_UNP16_WAVES) void k_hq_unpack16(const Unpa
             const unsigned mag = ((1u << K) | compact_even32(body)) - 1u;
             const int neg = (int)((hi >> ((30 - 2 * K) & 31)) & 1u);
             int v = neg ? (int)(0u - mag) : (int)mag;
-            if (!St<int16_t>::fits(v)) { escape(base + cnt, v); v = VC2_ST_SENTINEL; }
-            st[cnt++] = (short)v;
+            if constexpr (BY) { v = byte_of(base + cnt, v); sb[cnt++] = (signed char)v; }
+            else {
+              if (!St<int16_t>::fits(v)) { escape(base + cnt, v); v = VC2_ST_SENTINEL; }
+              st[cnt++] = (short)v;
+            }
             used = 2 * K + 2;
           } else { // longer than 32 bits (outside the reference's domain): bit-serial, wraps like the oracle
             unsigned value = 1;
@@ -2338,13 +2363,25 @@ __global__ __launch_bounds__(64 * VC2_UNP16_WAVES) void k_hq_unpack16(const Unpa
               v = (br.top() >> 31) ? (int)(0u - value) : (int)value;
               br.skip(pay, 1);
             }
-            if (!St<int16_t>::fits(v)) { escape(base + cnt, v); v = VC2_ST_SENTINEL; }
-            st[cnt++] = (short)v;
+            if constexpr (BY) { v = byte_of(base + cnt, v); sb[cnt++] = (signed char)v; }
+            else {
+              if (!St<int16_t>::fits(v)) { escape(base + cnt, v); v = VC2_ST_SENTINEL; }
+              st[cnt++] = (short)v;
+            }
           }
         }
       }
       br.skip(pay, used);
     }
+  };
+  // 16-bit rounds: everything where the band planes are 16-bit or there are none; with byte planes the record part of the
+  // component (heads, records) and the round that straddles its end -- byte rounds follow from the first round that starts
+  // in the planes (below).
+  const int n16 = BP8 ? min(n, p.bp.from[comp]) : n;
+  int base = 0;
+  for (; base < n16; base += UNP_N) {
+    const int room = min(UNP_N, n - base);
+    turns(std::false_type(), base, room);
     // flush: UNP_N / 8 lanes x 16 bytes per row (half a 128-byte line of the store).  The staging rows are private to the
     // wavefront, so only its own lanes have to agree (LDS operations of one wavefront execute in order): no workgroup
     // barrier, the four wavefronts of the workgroup drift apart freely.
@@ -2436,6 +2473,67 @@ __global__ __launch_bounds__(64 * VC2_UNP16_WAVES) void k_hq_unpack16(const Unpa
     for (int k = 0; k < UNP_PITCH; k += 8) *(int4 *)(st + k) = make_int4(0, 0, 0, 0);
     cnt = max(cnt - UNP_N, 0);
     if (cnt) *(int4 *)st = spill;
+  }
+  // Byte rounds (byte band planes): from here on every coefficient leaves as a byte of a plane, so the rows hold bytes --
+  // UNB_N = 64 coefficients plus 8 of slack in the 80 bytes a lane has: half the rounds (each ends in two syncs, a flush, a
+  // zero fill and a carry, and makes the wavefront wait for its slowest lane), a table entry's value bytes stored as they
+  // are, and a flush that only moves bytes: the range test of unp_bytes8 lives in the long-code path (byte_of), the only
+  // one that can make a value beyond a byte.
+  if constexpr (BP8) {
+    constexpr int UNB_N = 2 * UNP_N, UNB_PR = UNB_N / 8, UNB_PITCH = 2 * UNP_PITCH; // coefficients and pieces per row; bytes from row to row
+    static_assert(UNB_N + 8 <= UNB_PITCH, "a byte row and its slack fit the lane's part of the stage");
+    if (base < n) { // the carried coefficients (table values: |v| <= 30) become the first bytes of the row; behind them zeros
+      const int4 c16 = *(const int4 *)st;
+      *(int4 *)st = make_int4((int)__builtin_amdgcn_perm((unsigned)c16.y, (unsigned)c16.x, 0x06040200u),
+                              (int)__builtin_amdgcn_perm((unsigned)c16.w, (unsigned)c16.z, 0x06040200u), 0, 0);
+    }
+    const char *sw8 = (const char *)stage[wave];
+    char *planes = (char *)((int16_t *)p.store + (size_t)pic * p.store_stride);
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    for (; base < n; base += UNB_N) {
+      const int room = min(UNB_N, n - base);
+      turns(std::true_type(), base, room);
+      wave_lds_sync();
+      // flush: a piece is eight bytes of a row; the lanes take them in plane order as the 16-bit rounds do
+      for (int q = 0; q < UNB_PR;) {
+        if (8 * q >= room) break;
+        const int j0 = base + 8 * q;
+        int lw, ow, lbase;
+        int at = band_plane_at(p.bp, comp, n, j0, sy, sx, lw, ow, &lbase); // (lw, ow, lbase: the same in every lane)
+        if (!active) at = -1;
+        lw = __builtin_amdgcn_readfirstlane(lw);
+        const int lp = lw - 3, P = lw >= 4 ? 1 << lp : 1; // pieces per block row
+        if (lw >= 4 && q + P <= UNB_PR && ((j0 >> 3) & (P - 1)) == 0) { // (a whole row inside the round; else piece by piece)
+          for (int k = 0; k < P; ++k) {
+            const int t = lane + 64 * k, sl = t >> lp, pp = t & (P - 1);
+            const int at_t = __shfl(at, sl);
+            if (at_t >= 0) {
+              const v2i vb = *(const v2i *)(sw8 + sl * UNB_PITCH + 8 * (q + pp));
+              __builtin_nontemporal_store(vb, (__attribute__((address_space(1))) v2i *)(size_t)(planes + (size_t)(at_t + 8 * pp) + (size_t)lbase));
+            }
+          }
+          q += P;
+          continue;
+        }
+        if (at >= 0) {
+          const v2i vb = *(const v2i *)(sb + 8 * q);
+          char *dst = planes + (size_t)at + (size_t)lbase;
+          if (lw >= 3) __builtin_nontemporal_store(vb, (__attribute__((address_space(1))) v2i *)(size_t)dst);
+          else { // two rows of 4
+            __builtin_nontemporal_store(vb.x, (__attribute__((address_space(1))) int *)(size_t)dst);
+            __builtin_nontemporal_store(vb.y, (__attribute__((address_space(1))) int *)(size_t)(dst + ow));
+          }
+        }
+        ++q;
+      }
+      wave_lds_sync();
+      // coefficients decoded beyond the round move to the front of the row
+      const v2i spill = *(const v2i *)(sb + UNB_N);
+#pragma unroll
+      for (int k = 0; k < UNB_PITCH; k += 16) *(int4 *)(sb + k) = make_int4(0, 0, 0, 0);
+      cnt = max(cnt - UNB_N, 0);
+      if (cnt) *(v2i *)sb = spill;
+    }
   }
 }
 

@@ -1406,7 +1406,11 @@ static int run_pack(vc2hip_ctx *c, const Geom &g, int n, const PackJob &job) {
   // (the look-back pays from ~100 pictures per launch on: the grid puts the same tile of ALL pictures side by side, and a
   // picture's tile t - 1 is only that many workgroups ahead of tile t.  128 UHD pictures: 1.69 ms against 1.47 + 0.51 for
   // slots and compaction; 96: 1.46 = 1.46; 64: 1.15 against 0.75 + 0.25)
-  const bool one_pass = !gimg && !d_cbr_bytes &&
+  // Only where four slice images fit in LDS (image mode 0): the look-back counts tiles of FOUR slices (k_hq_pack16 has no other form; k_hq_pack's long modes were what overran) --
+  // the status words above are sized for them, k_hq_pack adds up four wavefronts' byte counts and takes the picture's length
+  // from tile (slices + 3) / 4 - 1.  Long slices (a scalar of 46 or more: two wavefronts or one per workgroup) made twice or
+  // four times as many tiles and ran the status words off their buffer: they go through the slots, whatever the flag
+  const bool one_pass = vc2_pack_image_mode(prefix, scalar) == 0 && !d_cbr_bytes &&
                         (!c->two_pass_vbr || (!c->force_two_pass_vbr && n >= VC2_ONE_PASS_MIN_PICTURES && vc2_pack_one_pass_default(p)));
   if (one_pass) {
     const long long lb_stride = (long long)((ns + 3) / 4) + 8;

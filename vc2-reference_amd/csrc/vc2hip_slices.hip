@@ -378,7 +378,9 @@ __device__ __forceinline__ void load8_tab(Coef8 &c, const ST *src, const int32_t
     else St<ST>::load8(src + j0, wide + j0, raw);
     const uint2 bands = *(const uint2 *)(band_lut + j0);
     // quant(), Quantisation.cpp:69-76, eight at a time: floor(4|v| / factor) as the truncated float product of |v| and
-    // the rounded-up 4 / factor (exact for |v| < 2^20, see k_cbr_search_reg), then ONE test whether any left that domain
+    // the rounded-up 4 / factor, then ONE test whether any left that domain.  Exact for |v| < 2^20 at every index 0 .. 115:
+    // k_cbr_search_reg's comment has the argument (4|v| < 2^22), tests/test_quant_ref.py every case of it; the first
+    // magnitude that fails is 1 761 441 at index 23, a factor 1.68 above the guard below
     int qq[8];
     float big = 0.f;
 #pragma unroll
@@ -1133,12 +1135,12 @@ __device__ __forceinline__ void bits8_tab(const ST *src, const int32_t *wide, in
       const unsigned m = __umulhi(t.x, a);
       qq[k] = (int)((m + ((a - m) >> 1)) >> t.y);
       a8[k] = a; qf8[k] = t.z;
-      dom |= a | (t.z - 2u);
+      dom |= a | (t.z - 2u) | t.z; // (| t.z: index 116's factor is INT_MIN, and INT_MIN - 2 is positive)
     }
     if (__any((int)dom < 0)) {
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        if ((int)(a8[k] | (qf8[k] - 2u)) < 0) qq[k] = (int)a8[k] / (int)qf8[k];
+        if ((int)(a8[k] | (qf8[k] - 2u) | qf8[k]) < 0) qq[k] = (int)a8[k] / (int)qf8[k];
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) { // only the length matters: the sign of the quantised value does not change it
@@ -1326,7 +1328,7 @@ __global__ __launch_bounds__(256) void k_cbr_search(const CbrParams p) {
 // The same search with the slice in registers: a lane keeps its eight luma and eight chroma magnitudes as floats for all
 // trials, the quantiser is one multiply by a rounded-up 4 / factor, and the code length comes from the exponent of
 // 4|c| / factor + 1 -- no LDS staging, no integer multiplies, no count-leading-zeros.
-//   quant (Quantisation.cpp:69-76): q = floor(4|c| / f).  With r = the smallest float >= 4 / f and |c| < 2^15:
+//   quant (Quantisation.cpp:69-76): q = floor(4|c| / f).  With r = the smallest float >= 4 / f and |c| < 2^20 (here: < 2^15):
 //     fl(|c| * r) lies in [4|c|/f, 4|c|/f * (1 + 2^-22)); 4|c|/f is a multiple of 1/f, so no integer lies in between as
 //     long as 4|c| < 2^22 -> truncation gives q exactly.
 //   SignedVLC bits (VLC.cpp:78-85): 1 for q = 0, else 2 floor(log2(q + 1)) + 2, and floor(log2(q + 1)) =
@@ -3786,12 +3788,12 @@ __device__ __forceinline__ void ld_diag_body(const LdEncParams &p, int d, int rs
       const unsigned m = __umulhi(t.x, a);
       qq[k] = (int)((m + ((a - m) >> 1)) >> t.y);
       a8[k] = a; qf8[k] = t.z;
-      dom |= a | (t.z - 2u);
+      dom |= a | (t.z - 2u) | t.z; // (| t.z: index 116's factor is INT_MIN, and INT_MIN - 2 is positive)
     }
     if (__any((int)dom < 0)) { // outside the reciprocal's domain: the literal division (see quant_core)
 #pragma unroll
       for (int k = 0; k < CPL; ++k)
-        if ((int)(a8[k] | (qf8[k] - 2u)) < 0) qq[k] = (int)a8[k] / (int)qf8[k];
+        if ((int)(a8[k] | (qf8[k] - 2u) | qf8[k]) < 0) qq[k] = (int)a8[k] / (int)qf8[k];
     }
 #pragma unroll
     for (int k = 0; k < CPL; ++k) { // only the length matters: the sign of the quantised value does not change it

@@ -33,7 +33,7 @@ enum { VC2HIP_DD97 = 0, VC2HIP_LEGALL = 1, VC2HIP_DD137 = 2, VC2HIP_HAAR0 = 3,
 /* ColourFormat, src/Library/Picture.h:17 */
 enum { VC2HIP_CF444 = 0, VC2HIP_CF422 = 1, VC2HIP_CF420 = 2 };
 /* Mode, src/EncodeStream/EncodeParams.h */
-enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2, VC2HIP_HQ_CAPPED = 3 };
+enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2, VC2HIP_HQ_CAPPED = 3, VC2HIP_HQ_CAPPED_FILL = 4 };
 /* VC2HIP_HQ_CAPPED (an extension; the reference has no such mode): constant quality under a per-picture byte cap, on the
  * encoding batch calls (vc2hip_encode_batch_dev, _fields_batch_dev, _recon_batch_dev and the host-buffer and _begin / _end
  * calls that reach them).  vc2hip_coding_params is read as for HQ_CONSTQ except
@@ -53,8 +53,28 @@ enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2, VC2HIP_HQ_CAPPED 
  * q_index outside 0 .. 115 or compressed_bytes < 1: VC2HIP_EINVAL, nothing launched.  Every call that does not encode
  * (decoders, vc2hip_picture_header, the stream calls, vc2hip_max_payload_bytes) reads the mode as HQ_CONSTQ: the stream is
  * a plain HQ VBR stream, and payload_stride >= vc2hip_max_payload_bytes as for HQ_CONSTQ.
- * Not provided: a -m option of the command-line tools, rate control per slice inside a picture, LD
- * (vc2hip_encode_picture_ld refuses every mode but VC2HIP_LD). */
+ * Not provided: a -m option of the command-line tools, LD (vc2hip_encode_picture_ld refuses every mode but VC2HIP_LD);
+ * indices per slice inside a picture: VC2HIP_HQ_CAPPED_FILL below, and no more than it says. */
+/* VC2HIP_HQ_CAPPED_FILL (an extension): HQ_CAPPED, with the bytes the cap leaves spent on a finer index in some slices.
+ * Accepted wherever HQ_CAPPED is, with HQ_CAPPED's parameters and refusals.  Per picture, with ns = y_slices * x_slices and
+ * the slices numbered in raster order:
+ *   1. q_i is HQ_CAPPED's.  If q_i == q_index, or the picture does not fit at q_i (nothing fits: q_i = 115), every slice
+ *      gets q_i and the picture is byte for byte HQ_CAPPED's.
+ *   2. Otherwise len_s(q) is slice s's bytes at index q (prefix + 4 + its three component lengths), spare = compressed_bytes
+ *      - sum of len_s(q_i) >= 0.  Slice s is eligible if the slice coder codes it at q_i - 1 (no length byte above 255, no
+ *      code beyond 32 bits); its cost is len_s(q_i - 1) - len_s(q_i) >= 0.  An ineligible slice stays at q_i and costs 0.
+ *   3. B = the number of bits of ns - 1 (0 for ns = 1).  Position k = 0 .. 2^B - 1 visits slice rev_B(k), the B-bit reversal
+ *      of k; positions whose slice is >= ns are skipped.  (The promoted slices spread over the picture.)
+ *   4. With C_k the running sum of the costs through position k inclusive (64-bit), the slice at position k gets q_i - 1
+ *      iff it is eligible and C_k <= spare; every other slice gets q_i.  Slices of cost 0 inside that prefix are promoted too.
+ *   5. Payload, d_lens, d_recon, d_sse and d_qidx (the mix, also with d_payload == NULL) are those of the slice coder for
+ *      that index map.  d_lens[i] <= compressed_bytes whenever HQ_CAPPED's is, and d_lens[i] >= HQ_CAPPED's.
+ * Trying raises no error; errors of the final encode surface at vc2hip_sync.  The result is a plain HQ VBR stream; every call
+ * that does not encode reads the mode as HQ_CONSTQ.  The batch contract holds as for HQ_CAPPED (asynchronous, nothing
+ * allocated / copied / waited for after the first call of a geometry and n, graph capture, lanes, layouts, packed formats,
+ * a caller's matrix, every context flag); VC2HIP_FLAG_CAP_GENERAL sends the third measurement to the general kernel too.
+ * Not provided: the capped transcode (vc2hip_transcode_batch_dev keeps one index per picture), more than two indices per
+ * picture, a choice of slices by distortion, LD, the command-line tools. */
 #define VC2HIP_CAP_Q_TOP 115
 
 enum {
@@ -200,7 +220,7 @@ typedef struct {
 typedef struct {
   int kernel, depth;      /* -k -d                                              */
   int y_slices, x_slices; /* from vc2hip_slice_size_is_valid                    */
-  int mode;               /* VC2HIP_HQ_CONSTQ / HQ_CBR / LD / HQ_CAPPED         */
+  int mode;               /* VC2HIP_HQ_CONSTQ / HQ_CBR / LD / HQ_CAPPED[_FILL]  */
   int q_index;            /* ConstQ                                             */
   int compressed_bytes;   /* CBR / LD picture byte budget (-s)                  */
   int prefix, scalar;     /* -P -S                                              */
@@ -485,7 +505,7 @@ int vc2hip_decode_reduced_batch_dev(vc2hip_ctx *ctx, const void *d_payload, size
  *   d_qidx      n x y_slices * x_slices int32, raster order, or NULL: the index of every slice as the encoder used it --
  *               q_index everywhere for HQ_ConstQ, the result of the search for HQ_CBR and LD
  *               (HQ_CAPPED: the picture's q_i in every slice of picture i, also with d_payload == NULL -- the
- *               measurement runs whether or not a payload is written)
+ *               measurement runs whether or not a payload is written; HQ_CAPPED_FILL: the mix of q_i and q_i - 1)
  * All modes, wavelets (Daub97 included), chroma formats, word_bytes 1 - 4, padded sizes, prefix and scalar; every context flag
  * gives the same bytes.  LD: the reconstruction is the DECODER's (DC-predicted LL band).  The reference's own -o Decoded
  * dequantises LD pictures without the prediction (EncodeStream.cpp:651); this call does not copy that.
@@ -514,7 +534,7 @@ int vc2hip_encode_recon_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
  *   top_field_first  1: the first field is rows 0, 2, 4, ... of every plane; 0: rows 1, 3, 5, ...
  *   cp          ONE FIELD picture: slices valid for the field heights (frame height / 2, frame chroma height / 2),
  *               compressed_bytes the field's budget (EncodeStream passes -s / 2).  cp is used as given: no budget arithmetic.
- * VC2HIP_HQ_CAPPED: cp is one field's, as for every other mode, and the cap is per field.
+ * VC2HIP_HQ_CAPPED, VC2HIP_HQ_CAPPED_FILL: cp is one field's, as for every other mode, and the cap is per field.
  * Otherwise the batch calls' contract above, word for word: all modes, wavelets, chroma formats, word_bytes 1 - 4 and
  * chroma_bit_depth; 16-byte alignment; asynchronous on the ctx stream, errors at vc2hip_sync; vc2hip_set_streams splits by
  * whole frames (lane i: frames [first, first + count), slots [2 first, 2 (first + count))), results identical.

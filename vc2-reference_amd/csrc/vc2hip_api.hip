@@ -134,6 +134,7 @@ enum { B_RAW, B_STORE, B_STOREW, B_LL0, B_LLW, B_QIDX, B_SLOTS, B_SIZES, B_OFFS,
        B_RSTORE, B_RSTOREW, // encode_recon_batch_dev: the quantised coefficients in the decoder's layout
        B_PLANE_QM,          // plane_inverse: the device copy of the quantisation matrix in plane_qm_held
        B_CAPTAB,            // HQ_CAPPED: the per-picture length table (vc2hip_cap.h)
+       B_CAPCOST,           // HQ_CAPPED_FILL: the per-slice costs of the third round
        B_PKIN, B_PKOUT,     // vc2hip_set_packed_format: the planar staging of a call's input and of its output pictures
        B_TCLEN, B_TCQ,      // vc2hip_transcode_batch_dev: the indices handed to the slice coder, the pictures' indices of the capped form
        B_CBRB2, B_CBRO2,    // budget_tables' second slot: the output side of vc2hip_transcode_cbr_batch_dev
@@ -970,7 +971,7 @@ static size_t max_slice_bytes(int prefix, int scalar) { return (size_t)prefix + 
 extern "C" size_t vc2hip_max_payload_bytes(const vc2hip_picture_format *f, const vc2hip_coding_params *cp) {
   (void)f;
   const size_t n = (size_t)cp->y_slices * cp->x_slices;
-  if (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CAPPED) return n * max_slice_bytes(cp->prefix, cp->scalar);
+  if (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CAPPED || cp->mode == VC2HIP_HQ_CAPPED_FILL) return n * max_slice_bytes(cp->prefix, cp->scalar);
   if (cp->mode == VC2HIP_HQ_CBR) return (size_t)cp->compressed_bytes + n * (cp->prefix + (size_t)cp->scalar + 4);
   return (size_t)cp->compressed_bytes + n;
 }
@@ -2185,9 +2186,11 @@ static int batch_args(vc2hip_ctx *c, int n, const vc2hip_picture_format *f, cons
 }
 // what the three encoding calls refuse in cp; g: the coded picture's geometry
 static int encode_check(vc2hip_ctx *c, const vc2hip_picture_format *f, const vc2hip_coding_params *cp, Geom &g) {
-  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD && cp->mode != VC2HIP_HQ_CAPPED) return set_err(c, VC2HIP_EINVAL);
-  if (cp->mode == VC2HIP_HQ_CAPPED && (cp->q_index < 0 || cp->q_index > VC2_CAP_Q_TOP || cp->compressed_bytes < 1))
-    return set_err(c, VC2HIP_EINVAL, "HQ_CAPPED: q_index 0 .. 115, compressed_bytes >= 1");
+  const bool capped = cp->mode == VC2HIP_HQ_CAPPED || cp->mode == VC2HIP_HQ_CAPPED_FILL;
+  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_LD && !capped) return set_err(c, VC2HIP_EINVAL);
+  if (capped && (cp->q_index < 0 || cp->q_index > VC2_CAP_Q_TOP || cp->compressed_bytes < 1))
+    return set_err(c, VC2HIP_EINVAL, cp->mode == VC2HIP_HQ_CAPPED ? "HQ_CAPPED: q_index 0 .. 115, compressed_bytes >= 1"
+                                                                   : "HQ_CAPPED_FILL: q_index 0 .. 115, compressed_bytes >= 1");
   if (cp->mode != VC2HIP_LD && (cp->scalar < 1 || cp->prefix < 0)) return set_err(c, VC2HIP_EINVAL);
   const int rc = picture_geom(g, f, cp, false);
   return rc ? set_err(c, rc) : VC2HIP_OK;
@@ -2296,10 +2299,13 @@ static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, 
     CbrParams p;
     fill_cbr(p, g, st, d_q, b.bytes, cp->scalar, qm, c->cbr_general, c->d_err);
     vc2_launch_cbr(c->L, p, n, c->stream);
-  } else if (cp->mode == VC2HIP_HQ_CAPPED) { // one index per picture, found on the device (vc2hip_cap.h)
+  } else if (cp->mode == VC2HIP_HQ_CAPPED || cp->mode == VC2HIP_HQ_CAPPED_FILL) {
+    // one index per picture, found on the device (vc2hip_cap.h); HQ_CAPPED_FILL: then q_i - 1 in as
+    // many slices as the cap's spare bytes pay for (section 28: the cost buffer switches the third round and the fill on)
     CapParams p;
     memset(&p, 0, sizeof p);
     NEED(c, B_CAPTAB, (size_t)n * VC2_CAP_ROW * 8, p.table);
+    if (cp->mode == VC2HIP_HQ_CAPPED_FILL) NEED(c, B_CAPCOST, (size_t)n * ns * 4, p.cost);
     HIPCHK(c, hipMemsetAsync(p.table, 0, (size_t)n * VC2_CAP_ROW * 8, c->stream));
     fill_cbr(p.s, g, st, d_q, b.bytes, cp->scalar, qm, c->cap_general, c->d_err); // (no budgets: the cap is the picture's)
     p.prefix = cp->prefix; p.floor = cp->q_index; p.cap = (unsigned long long)cp->compressed_bytes;
@@ -2602,7 +2608,7 @@ struct HeaderBits { // MSB-first writer of DataUnit.cpp's BitWriter
 bool stream_cp_ok(const vc2hip_coding_params *cp) {
   if (!cp || cp->kernel < 0 || cp->kernel > 6 || cp->depth < 0 || cp->y_slices < 1 || cp->x_slices < 1) return false;
   if (cp->mode == VC2HIP_LD) return cp->compressed_bytes > 0;
-  return (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CBR || cp->mode == VC2HIP_HQ_CAPPED) && cp->prefix >= 0 && cp->scalar >= 1;
+  return (cp->mode == VC2HIP_HQ_CONSTQ || cp->mode == VC2HIP_HQ_CBR || cp->mode == VC2HIP_HQ_CAPPED || cp->mode == VC2HIP_HQ_CAPPED_FILL) && cp->prefix >= 0 && cp->scalar >= 1;
 }
 // what the transform parameters carry after the slice counts: prefix, scalar (HQ) or the slice-bytes fraction in lowest
 // terms (LD: utils::rationalise(pictureBytes, slices), EncodeStream.cpp:263)
@@ -2919,7 +2925,7 @@ extern "C" int vc2hip_transcode_batch_dev(vc2hip_ctx *c, const void *d_payload_i
                           {{d_payload_in, 16}, {d_lens_in, 8}, {d_payload_out, 16}, {d_lens_out, 8}, {d_qidx, 4, true}})) return rc;
   if (!tp) return set_err(c, VC2HIP_EINVAL);
   if (payload_stride_out & 15) return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
-  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_HQ_CAPPED)
+  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CBR && cp->mode != VC2HIP_HQ_CAPPED && cp->mode != VC2HIP_HQ_CAPPED_FILL)
     return set_err(c, VC2HIP_EINVAL, "transcode_batch_dev: HQ pictures only");
   if (tp->q_index < 0 || tp->q_index > VC2_CAP_Q_TOP || tp->cap_bytes < 0)
     return set_err(c, VC2HIP_EINVAL, "transcode_batch_dev: q_index 0 .. 115, cap_bytes >= 0");
@@ -3005,7 +3011,7 @@ extern "C" int vc2hip_transcode_cbr_batch_dev(vc2hip_ctx *c, const void *d_paylo
                           {{d_payload_in, 16}, {d_lens_in, 8}, {d_payload_out, 16}, {d_lens_out, 8}, {d_qidx, 4, true}})) return rc;
   if (!cp_out) return set_err(c, VC2HIP_EINVAL);
   if (payload_stride_out & 15) return set_err(c, VC2HIP_EINVAL, "device buffers and the payload stride must be 16-byte aligned");
-  if (cp_in->mode != VC2HIP_HQ_CONSTQ && cp_in->mode != VC2HIP_HQ_CBR && cp_in->mode != VC2HIP_HQ_CAPPED)
+  if (cp_in->mode != VC2HIP_HQ_CONSTQ && cp_in->mode != VC2HIP_HQ_CBR && cp_in->mode != VC2HIP_HQ_CAPPED && cp_in->mode != VC2HIP_HQ_CAPPED_FILL)
     return set_err(c, VC2HIP_EINVAL, "transcode_cbr_batch_dev: HQ pictures only");
   if (cp_out->mode != VC2HIP_HQ_CBR) return set_err(c, VC2HIP_EINVAL, "transcode_cbr_batch_dev: cp_out must be HQ_CBR");
   if (cp_out->kernel != cp_in->kernel || cp_out->depth != cp_in->depth || cp_out->y_slices != cp_in->y_slices || cp_out->x_slices != cp_in->x_slices)

@@ -7,18 +7,34 @@
 // A measurement is a trial, as TRIAL is in bits8_tab: a candidate at which the slice coder would raise VC2HIP_ESCALAR or
 // VC2HIP_ECODE32 does not fit (its table entry saturates, VC2_CAP_NOFIT) and raises nothing.
 // (Included by vc2hip_slices.hip behind the HQ_CBR search, whose measurements these kernels repeat.)
+//
+// HQ_CAPPED_FILL adds, for the pictures that left the floor and fit at their index q_i:
+//   round 3  measure every SLICE at q_i - 1 and q_i: its cost len_s(q_i - 1) - len_s(q_i), or VC2_CAP_NOCOST where the slice
+//            coder would raise at q_i - 1, into CapParams::cost (the FILL instantiations of the two measuring kernels)
+//   fill     k_cap_fill: along the bit-reversed visit order, the slices whose running cost stays within cap - L(q_i) get q_i - 1
+// q_i, the fill flag and the spare bytes travel in words 27 .. 29 of the picture's table row (k_cap_pick).
 #pragma once
+#include <type_traits>
 
 struct CapCand { int q0, step, nc, off; }; // candidate k < nc is index q0 + step * k; its sum is word off + k of the picture's row
+template <bool FILL>
 __device__ __forceinline__ CapCand cap_candidates(const CapParams &p, int pic) {
   CapCand c;
-  if (p.round == 0) {
+  if constexpr (FILL) { // the third round: q_i - 1 and q_i, per slice (off: unused)
+    const unsigned long long *row = p.table + (size_t)pic * VC2_CAP_ROW;
+    c.q0 = (int)row[VC2_CAP_QI] - 1; c.step = 1; c.nc = row[VC2_CAP_FILL] ? 2 : 0; c.off = 0;
+  } else if (p.round == 0) {
     c.q0 = p.floor; c.step = 8; c.nc = (VC2_CAP_Q_TOP - p.floor) / 8 + 1; c.off = 0;
   } else {
     const unsigned long long *row = p.table + (size_t)pic * VC2_CAP_ROW;
     c.q0 = (int)row[VC2_CAP_BASE] + 1; c.step = 1; c.nc = min((int)row[VC2_CAP_COUNT], 7); c.off = VC2_CAP_R2;
   }
   return c;
+}
+// the third round's result of one slice, from the lanes that hold its bytes at q_i - 1 (lane 0) and at q_i (lane 1)
+__device__ __forceinline__ void cap_store_cost(const CapParams &p, int pic, int slice, unsigned long long val, int lane) {
+  const unsigned long long v0 = __shfl(val, 0), v1 = __shfl(val, 1);
+  if (lane == 0) p.cost[(size_t)pic * p.s.n_slices + slice] = v0 >= VC2_CAP_NOFIT ? VC2_CAP_NOCOST : (unsigned)(v0 - v1);
 }
 
 // component_bits<true, false> that also says whether a code passes 32 bits (big), and touches no error flag
@@ -49,12 +65,12 @@ __device__ __forceinline__ int cap_component_bits(Src src, int n, int n0, int q,
 
 // The general form: one wavefront per slice, any geometry and either store; the slice staged in LDS, or (GLOBAL) read from
 // the store at every candidate.  only_marked: the pass behind k_cap_measure16 over the slices it handed back.
-template <class ST, bool GLOBAL>
+template <class ST, bool GLOBAL, bool FILL>
 __global__ __launch_bounds__(256) void k_cap_measure(const CapParams p) {
   extern __shared__ __attribute__((aligned(16))) int lds_i[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpw = blockDim.x >> 6;
   const int pic = blockIdx.y;
-  const CapCand cd = cap_candidates(p, pic);
+  const CapCand cd = cap_candidates<FILL>(p, pic);
   if (cd.nc <= 0) return; // (no workgroup barrier anywhere in this kernel)
   unsigned long long mine = 0; // lane k: candidate k's bytes over this wavefront's slices
   auto measure = [&](const int slice) {
@@ -94,7 +110,8 @@ __global__ __launch_bounds__(256) void k_cap_measure(const CapParams p) {
       if (lane == k) val = big ? VC2_CAP_NOFIT : (unsigned long long)(p.prefix + 4 + need);
       if (!big && need == 0) break; // no coefficient left, at this index and at every larger one
     }
-    mine += val;
+    if constexpr (FILL) cap_store_cost(p, pic, slice, val, lane);
+    else mine += val;
     if constexpr (!GLOBAL) wave_lds_sync();
   };
   const int first = blockIdx.x * wpw + wave;
@@ -106,7 +123,8 @@ __global__ __launch_bounds__(256) void k_cap_measure(const CapParams p) {
       for (unsigned long long m = __ballot(marked); m; m &= m - 1) measure(base + __ffsll((long long)m) - 1);
     }
   }
-  if (lane < cd.nc && mine) atomicAdd(&p.table[(size_t)pic * VC2_CAP_ROW + cd.off + lane], mine);
+  if constexpr (!FILL)
+    if (lane < cd.nc && mine) atomicAdd(&p.table[(size_t)pic * VC2_CAP_ROW + cd.off + lane], mine);
 }
 
 // The fast form: the lane layout and the float measurement of k_cbr_search16 (vc2hip_cbr16.h: cbr16_plan, need_bytes) for
@@ -115,6 +133,7 @@ __global__ __launch_bounds__(256) void k_cap_measure(const CapParams p) {
 // The quantiser table stops at index 79 as k_cbr_search16's does, and larger adjusted indices read entry 79; here that is
 // exact, so no index is handed back: a magnitude of the 16-bit store is at most 32767, 4 * 32767 < factor(79) = 3 526 975
 // <= factor(a) for 79 <= a <= 115, so both the true quotient and fl(|c| * r79) < 1 are zero.
+template <bool FILL>
 __global__ __launch_bounds__(256, VC2_CBR16_WPE) void k_cap_measure16(const CapParams p) {
   __shared__ uint4 s_tab[80]; // by quantiser index: (rounded-up 4 / factor as a float, -, -, -)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -122,7 +141,7 @@ __global__ __launch_bounds__(256, VC2_CBR16_WPE) void k_cap_measure16(const CapP
   if (threadIdx.x < 80) s_tab[threadIdx.x] = make_uint4(__float_as_uint(c_qs.inv4[threadIdx.x]), 0u, 0u, 0u);
   const unsigned lq = p.s.lane8[lane];
   const int headY = (int)p.s.lane8[64], headC = (int)p.s.lane8[65], runsY = (int)p.s.lane8[66], runsC = (int)p.s.lane8[67];
-  const CapCand cd = cap_candidates(p, pic);
+  const CapCand cd = cap_candidates<FILL>(p, pic);
   __syncthreads();
   if (cd.nc <= 0) return;
   const bool has_y = lane < runsY, has_c = lane < 2 * runsC;
@@ -211,14 +230,18 @@ __global__ __launch_bounds__(256, VC2_CBR16_WPE) void k_cap_measure16(const CapP
       if (lane == k) val = bad ? VC2_CAP_NOFIT : (unsigned long long)(p.prefix + 4 + need);
       if (!bad && need == 0) break;
     }
-    mine += val;
+    if constexpr (FILL) cap_store_cost(p, pic, slice, val, lane);
+    else mine += val;
   }
-  if (lane < cd.nc && mine) atomicAdd(&p.table[(size_t)pic * VC2_CAP_ROW + cd.off + lane], mine);
+  if constexpr (!FILL)
+    if (lane < cd.nc && mine) atomicAdd(&p.table[(size_t)pic * VC2_CAP_ROW + cd.off + lane], mine);
 }
 
 // The pick, per picture.  Round 1 (one thread): the first fitting candidate closes a bracket of eight indices whose lower
 // end does not fit -- base, the count of indices to measure inside it, and the index if none of those fits.  Round 2: the
-// smallest fitting index of the bracket, written to the picture's n_slices entries of qidx.
+// smallest fitting index of the bracket, written to the picture's n_slices entries of qidx -- and, for HQ_CAPPED_FILL, q_i,
+// whether the picture is to be filled (it left the floor and fits at q_i) and its spare bytes cap - L(q_i), L(q_i) from
+// the table: the round-2 entry that fitted, or the round-1 entry of an index floor + 8 k.
 __global__ __launch_bounds__(256) void k_cap_pick(const CapParams p) {
   const int pic = blockIdx.y;
   unsigned long long *row = p.table + (size_t)pic * VC2_CAP_ROW;
@@ -237,9 +260,57 @@ __global__ __launch_bounds__(256) void k_cap_pick(const CapParams p) {
   }
   const int base = (int)row[VC2_CAP_BASE], count = min((int)row[VC2_CAP_COUNT], 7);
   int q = (int)row[VC2_CAP_ELSE];
-  for (int j = count - 1; j >= 0; --j) if (fits(row[VC2_CAP_R2 + j])) q = base + 1 + j;
+  int hit = -1;
+  for (int j = count - 1; j >= 0; --j) if (fits(row[VC2_CAP_R2 + j])) { q = base + 1 + j; hit = j; }
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < p.s.n_slices) p.s.qidx[(size_t)pic * p.s.n_slices + i] = q;
+  if (i == 0) { // (words no thread of this launch reads)
+    const unsigned long long len = hit >= 0 ? row[VC2_CAP_R2 + hit] : ((q - p.floor) % 8 == 0 ? row[(q - p.floor) / 8] : VC2_CAP_NOFIT);
+    const bool fill = q > p.floor && fits(len);
+    row[VC2_CAP_QI] = (unsigned long long)q; row[VC2_CAP_FILL] = fill ? 1ull : 0ull; row[VC2_CAP_SPARE] = fill ? p.cap - len : 0ull;
+  }
+}
+
+// HQ_CAPPED_FILL's index map, one workgroup per picture.  B = the bits of n_slices - 1; position k = 0 .. 2^B - 1 visits
+// slice rev_B(k) (positions past the picture are skipped), and the slice there gets q_i - 1 iff it has a cost and the running
+// sum of the costs through k, in 64 bits, is at most the spare bytes.  256 positions per turn: an inclusive scan in each
+// wavefront, the four totals through LDS, the carry in a register.  Pictures with nothing to fill keep k_cap_pick's indices.
+__global__ __launch_bounds__(256) void k_cap_fill(const CapParams p) {
+  __shared__ unsigned long long s_tot[4];
+  const int pic = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long *row = p.table + (size_t)pic * VC2_CAP_ROW;
+  if (!row[VC2_CAP_FILL]) return; // (the whole workgroup)
+  const int ns = p.s.n_slices, qi = (int)row[VC2_CAP_QI];
+  const unsigned long long spare = row[VC2_CAP_SPARE];
+  const int bits = ns > 1 ? 32 - __clz(ns - 1) : 0;
+  const unsigned *cost = p.cost + (size_t)pic * ns;
+  int32_t *q = p.s.qidx + (size_t)pic * ns;
+  unsigned long long carry = 0;
+  for (int k0 = 0; k0 < (1 << bits); k0 += 256) {
+    const int k = k0 + (int)threadIdx.x;
+    const int slice = bits ? (int)(__brev((unsigned)k) >> (32 - bits)) : 0;
+    const bool valid = k < (1 << bits) && slice < ns;
+    const unsigned c = valid ? cost[slice] : VC2_CAP_NOCOST;
+    const bool eligible = c != VC2_CAP_NOCOST;
+    unsigned long long v = eligible ? (unsigned long long)c : 0ull;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long t = __shfl_up(v, d);
+      if (lane >= d) v += t;
+    }
+    if (lane == 63) s_tot[wave] = v;
+    __syncthreads();
+    unsigned long long before = carry, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const unsigned long long t = s_tot[w];
+      if (w < wave) before += t;
+      total += t;
+    }
+    if (valid) q[slice] = eligible && before + v <= spare ? qi - 1 : qi;
+    carry += total;
+    __syncthreads(); // s_tot is written again
+  }
 }
 
 void vc2_launch_cap(Launcher &L, const CapParams &p0, int n_pictures, hipStream_t s) {
@@ -256,29 +327,36 @@ void vc2_launch_cap(Launcher &L, const CapParams &p0, int n_pictures, hipStream_
   const size_t per_wave = (size_t)g.slice_coefs * 4;
   const bool global = per_wave > 160 * 1024; // the slice does not fit in LDS: every candidate reads it from the store
   const int wpw = global ? 4 : std::max(1, std::min(4, (int)((160 * 1024) / per_wave)));
-  for (int round = 0; round < 2; ++round) {
-    vc2_prof_begin(L, round ? "cap_measure2" : "cap_measure1", s);
+  static const char *const names[3] = {"cap_measure1", "cap_measure2", "cap_measure3"};
+  for (int round = 0; round < (p.cost ? 3 : 2); ++round) {
+    const bool fill = round == 2;
+    vc2_prof_begin(L, names[round], s);
     p.round = p16.round = round;
     p.s.only_marked = 0;
     if (fast) {
       const int per_wg = 4 * CBR_SPW;
-      VC2_LAUNCH(L, k_cap_measure16, dim3((g.n_slices + per_wg - 1) / per_wg, n_pictures), dim3(256), 0, s, p16);
+      if (fill) VC2_LAUNCH(L, k_cap_measure16<true>, dim3((g.n_slices + per_wg - 1) / per_wg, n_pictures), dim3(256), 0, s, p16);
+      else VC2_LAUNCH(L, k_cap_measure16<false>, dim3((g.n_slices + per_wg - 1) / per_wg, n_pictures), dim3(256), 0, s, p16);
       p.s.only_marked = 1;
     }
     const int gx = p.s.only_marked ? std::min((g.n_slices + wpw - 1) / wpw, 64) : (g.n_slices + wpw - 1) / wpw;
-    if (global) {
-      if (g.store16) VC2_LAUNCH(L, (k_cap_measure<int16_t, true>), dim3(gx, n_pictures), dim3(64 * wpw), 0, s, p);
-      else VC2_LAUNCH(L, (k_cap_measure<int32_t, true>), dim3(gx, n_pictures), dim3(64 * wpw), 0, s, p);
-    } else if (g.store16) {
-      vc2_allow_lds((const void *)k_cap_measure<int16_t, false>, 160 * 1024);
-      VC2_LAUNCH(L, (k_cap_measure<int16_t, false>), dim3(gx, n_pictures), dim3(64 * wpw), wpw * per_wave, s, p);
-    } else {
-      vc2_allow_lds((const void *)k_cap_measure<int32_t, false>, 160 * 1024);
-      VC2_LAUNCH(L, (k_cap_measure<int32_t, false>), dim3(gx, n_pictures), dim3(64 * wpw), wpw * per_wave, s, p);
-    }
+    const dim3 grid(gx, n_pictures), block(64 * wpw);
+    auto general = [&](auto st, auto gl, auto fl) { // one launch of k_cap_measure<ST, GLOBAL, FILL>
+      using ST = decltype(st);
+      constexpr bool GL = decltype(gl)::value, FL = decltype(fl)::value;
+      if (!GL) vc2_allow_lds((const void *)k_cap_measure<ST, GL, FL>, 160 * 1024);
+      VC2_LAUNCH(L, (k_cap_measure<ST, GL, FL>), grid, block, GL ? 0 : wpw * per_wave, s, p);
+    };
+    auto by_store = [&](auto gl, auto fl) {
+      if (g.store16) general(int16_t(), gl, fl);
+      else general(int32_t(), gl, fl);
+    };
+    if (global) { if (fill) by_store(std::true_type(), std::true_type()); else by_store(std::true_type(), std::false_type()); }
+    else { if (fill) by_store(std::false_type(), std::true_type()); else by_store(std::false_type(), std::false_type()); }
     vc2_prof_end(L, s);
-    vc2_prof_begin(L, "cap_pick", s);
-    VC2_LAUNCH(L, k_cap_pick, dim3(round ? (g.n_slices + 255) / 256 : 1, n_pictures), dim3(256), 0, s, p);
+    vc2_prof_begin(L, fill ? "cap_fill" : "cap_pick", s);
+    if (fill) VC2_LAUNCH(L, k_cap_fill, dim3(1, n_pictures), dim3(256), 0, s, p);
+    else VC2_LAUNCH(L, k_cap_pick, dim3(round ? (g.n_slices + 255) / 256 : 1, n_pictures), dim3(256), 0, s, p);
     vc2_prof_end(L, s);
   }
 }

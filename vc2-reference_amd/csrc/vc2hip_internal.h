@@ -337,19 +337,26 @@ struct CbrParams {
 //   [0 .. 14]  round 1: the picture's payload bytes at floor + 8 k (a candidate that cannot be coded: >= VC2_CAP_NOFIT)
 //   [16 .. 22] round 2: the same at base + 1 + j, j < count
 //   [24] base, [25] count, [26] the index if none of round 2 fits (written by the first pick)
+//   [27] q_i, [28] fill: 1 where the picture left the floor and fits at q_i, [29] spare = cap - L(q_i)
+//              (written by the second pick: what HQ_CAPPED_FILL's third round and k_cap_fill read)
 #define VC2_CAP_Q_TOP 115
 #define VC2_CAP_ROW 32
 #define VC2_CAP_R2 16
 #define VC2_CAP_BASE 24
 #define VC2_CAP_COUNT 25
 #define VC2_CAP_ELSE 26
+#define VC2_CAP_QI 27
+#define VC2_CAP_FILL 28
+#define VC2_CAP_SPARE 29
 #define VC2_CAP_NOFIT (1ull << 40)
+#define VC2_CAP_NOCOST 0xFFFFFFFFu // HQ_CAPPED_FILL: the slice cannot be coded at q_i - 1
 struct CapParams {
   CbrParams s;                // store, geometry, matrix as the HQ_CBR search has them; qidx: the marks of the handed-back slices, then the result
   unsigned long long *table;  // n_pictures * VC2_CAP_ROW, zero before the first round
   unsigned long long cap;
   int prefix, floor;
-  int round;                  // 0 / 1
+  int round;                  // 0 / 1; 2: HQ_CAPPED_FILL's per-slice round
+  unsigned *cost;             // HQ_CAPPED_FILL (null otherwise): n_pictures * n_slices, len_s(q_i - 1) - len_s(q_i) or VC2_CAP_NOCOST
 };
 
 // ------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ FLAGS = {"STORE32": 0x001, "NO_STREAM": 0x002, "NO_PAIR": 0x004, "NO_BANDPLANES"
 
 KERNELS = {"DD97": 0, "LeGall": 1, "DD137": 2, "Haar0": 3, "Haar1": 4, "Fidelity": 5, "Daub97": 6}
 CF = {"444": 0, "422": 1, "420": 2}
-MODES = {"HQ_ConstQ": 0, "HQ_CBR": 1, "LD": 2, "HQ_Capped": 3}  # HQ_Capped: q = the lowest index, s = the cap (include/vc2hip.h)
+MODES = {"HQ_ConstQ": 0, "HQ_CBR": 1, "LD": 2, "HQ_Capped": 3, "HQ_CappedFill": 4}  # HQ_Capped[Fill]: q = the lowest index, s = the cap (include/vc2hip.h)
 
 
 class Geom(C.Structure):

@@ -1424,7 +1424,8 @@ static int run_pack(vc2hip_ctx *c, const Geom &g, int n, const PackJob &job) {
     return VC2HIP_OK;
   }
   // (images kept in the slots themselves: room for the two guard words of an image)
-  const int slot = (int)((max_slice_bytes(prefix, scalar) + (gimg ? 8 : 0) + 15) & ~(size_t)15);
+  // (under HQ_CBR a slice is up to scalar - 1 bytes longer than that: V's room holds a remainder the length byte does not show)
+  const int slot = (int)((max_slice_bytes(prefix, scalar) + (gimg ? 8 : 0) + (d_cbr_bytes ? scalar - 1 : 0) + 15) & ~(size_t)15);
   uint8_t *slots; uint32_t *sizes, *offs;
   // Shared slots (below) hold WHOLE tiles: a picture's last tile has room for all its spt slices even when fewer exist
   // (1080p: 16200 slices in 1013 tiles of 16 = room for 16208).  Rounds 3 - 5 sized the buffer by the slice count; the

@@ -220,7 +220,7 @@ __global__ __launch_bounds__((MODE == 2 ? 64 * P16LB_WAVES : 256), (MODE == 2 ? 
   const int pic = LB ? blockIdx.x : blockIdx.y, tile = LB ? blockIdx.y : blockIdx.x;
   const int slice = tile * NW + wave;
   const bool active = slice < p.n_slices; // wave-uniform
-  const int img_q = ((p.prefix + 4 + 3 * 255 * p.scalar + 3) / 4 + 2 + 3) / 4; // image size in 16-byte pieces
+  const int img_q = ((p.prefix + 4 + 3 * 255 * p.scalar + p.scalar - 1 + 3) / 4 + 2 + 3) / 4; // image size in 16-byte pieces (the longest HQ_CBR slice: k_hq_pack)
   unsigned *lut = lds_u;                   // at LDS address 0: a look-up's address is the quotient's low byte times four
   uint4 *qt = (uint4 *)(lds_u + P16_LUT_N); // by quantiser index: g_p16_qt
   unsigned *img = lds_u + P16_LUT_N + 4 * 128 + wave * img_q * 4;
@@ -561,7 +561,7 @@ __global__ __launch_bounds__(192) void k_hq_pack16w(const PackParams p) {
   __shared__ int s_cnt[3];
   const int lane = threadIdx.x & 63, comp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wavefront = component
   const int pic = blockIdx.y, slice = blockIdx.x;
-  const int img_q = ((p.prefix + 4 + 3 * 255 * p.scalar + 3) / 4 + 2 + 3) / 4; // image size in 16-byte pieces
+  const int img_q = ((p.prefix + 4 + 3 * 255 * p.scalar + p.scalar - 1 + 3) / 4 + 2 + 3) / 4; // image size in 16-byte pieces (the longest HQ_CBR slice: k_hq_pack)
   unsigned *lut = lds_u;
   uint4 *qt = (uint4 *)(lds_u + P16_LUT_N);
   unsigned *img = lds_u + P16_LUT_N + 4 * 128;
@@ -700,10 +700,10 @@ __global__ __launch_bounds__(192) void k_hq_pack16w(const PackParams p) {
 
 constexpr size_t P16_GUARD_BYTES = 128; // behind the last image: where p16_put's zero words of an all-zero tail may land
 static size_t pack16w_lds(int prefix, int scalar) {
-  const size_t img_q = (((size_t)prefix + 4 + 3 * 255 * (size_t)scalar + 3) / 4 + 2 + 3) / 4;
+  const size_t img_q = (((size_t)prefix + 4 + 3 * 255 * (size_t)scalar + (size_t)scalar - 1 + 3) / 4 + 2 + 3) / 4;
   return img_q * 16 + P16_LUT_N * 4 + 128 * 16 + P16_GUARD_BYTES;
 }
 static size_t pack16_lds(int prefix, int scalar, int waves = 4) {
-  const size_t img_q = (((size_t)prefix + 4 + 3 * 255 * (size_t)scalar + 3) / 4 + 2 + 3) / 4;
+  const size_t img_q = (((size_t)prefix + 4 + 3 * 255 * (size_t)scalar + (size_t)scalar - 1 + 3) / 4 + 2 + 3) / 4;
   return (size_t)waves * img_q * 16 + P16_LUT_N * 4 + 128 * 16 + P16_GUARD_BYTES;
 }

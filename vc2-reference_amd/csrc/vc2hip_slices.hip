@@ -517,7 +517,9 @@ __global__ __launch_bounds__(256) void k_hq_pack(const PackParams p) {
     tile = s_tile;
   }
   const int slice = (tile * nwv + wave) * S + seg;
-  const int img_words = (p.prefix + 4 + 3 * 255 * p.scalar + 3) / 4 + 2;
+  // (+ scalar - 1: under HQ_CBR V's room holds a remainder beyond three times 255 units, and the codes that fit in it --
+  // the '1's of V's trailing zeros -- are written there like any other; pack_lds has the same sum)
+  const int img_words = (p.prefix + 4 + 3 * 255 * p.scalar + p.scalar - 1 + 3) / 4 + 2;
   const bool active = slice < p.n_slices;
   unsigned *img = GIMG ? (unsigned *)(p.slots + ((size_t)pic * p.n_slices + (active ? slice : 0)) * p.slot_bytes)
                        : lds_u + (wave * S + seg) * img_words;
@@ -534,7 +536,8 @@ __global__ __launch_bounds__(256) void k_hq_pack(const PackParams p) {
     if (fast && p.quantise && active && sl * 8 + 8 <= p.comp_n[0])
       pre_y = *(const uint4 *)((const ST *)p.store + (size_t)pic * p.store_stride + (size_t)slice * p.slice_coefs + p.comp_off[0] + sl * 8);
   }
-  if (!GIMG || active) for (int i = sl; i < img_words; i += W) img[i] = 0;
+  // (GIMG: the whole slot, which run_pack sizes for the longest HQ_CBR slice)
+  if (!GIMG || active) for (int i = sl; i < (GIMG ? p.slot_bytes >> 2 : img_words); i += W) img[i] = 0;
   if (GIMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the zeros are in place before the first atomic OR
   build_vlc_lut(lut);
   if (fast && p.quantise) copy_band_lut(band_y, p.band_lut);
@@ -806,7 +809,7 @@ struct __attribute__((aligned(4))) Dword4 { unsigned x, y, z, w; }; // four dwor
 
 size_t vc2_pack_lds_bytes(int prefix, int scalar);
 static size_t pack_lds(int prefix, int scalar, int slices_per_wave, bool big_lut = false, int waves = 4, bool gimg = false) {
-  const size_t img_words = gimg ? 0 : ((size_t)prefix + 4 + 3 * 255 * (size_t)scalar + 3) / 4 + 2;
+  const size_t img_words = gimg ? 0 : ((size_t)prefix + 4 + 3 * 255 * (size_t)scalar + (size_t)scalar - 1 + 3) / 4 + 2; // (the longest HQ_CBR slice)
   return waves * slices_per_wave * img_words * 4 + VLC_LUT_N * 4 + 768 + waves * (size_t)slices_per_wave * 32 * 16 + (big_lut ? 4096 : 0);
 }
 // 0: four slice images fit in LDS; else the wavefronts per workgroup to use (2, 1), or -1: images in global memory

@@ -54,7 +54,8 @@ enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2, VC2HIP_HQ_CAPPED 
  * (decoders, vc2hip_picture_header, the stream calls, vc2hip_max_payload_bytes) reads the mode as HQ_CONSTQ: the stream is
  * a plain HQ VBR stream, and payload_stride >= vc2hip_max_payload_bytes as for HQ_CONSTQ.
  * Not provided: a -m option of the command-line tools, LD (vc2hip_encode_picture_ld refuses every mode but VC2HIP_LD);
- * indices per slice inside a picture: VC2HIP_HQ_CAPPED_FILL below, and no more than it says. */
+ * indices per slice chosen by the library beyond VC2HIP_HQ_CAPPED_FILL below (the caller's own per-slice weighting:
+ * vc2hip_set_index_offsets, under which q_i becomes a base that every slice offsets). */
 /* VC2HIP_HQ_CAPPED_FILL (an extension): HQ_CAPPED, with the bytes the cap leaves spent on a finer index in some slices.
  * Accepted wherever HQ_CAPPED is, with HQ_CAPPED's parameters and refusals.  Per picture, with ns = y_slices * x_slices and
  * the slices numbered in raster order:
@@ -74,7 +75,8 @@ enum { VC2HIP_HQ_CONSTQ = 0, VC2HIP_HQ_CBR = 1, VC2HIP_LD = 2, VC2HIP_HQ_CAPPED 
  * allocated / copied / waited for after the first call of a geometry and n, graph capture, lanes, layouts, packed formats,
  * a caller's matrix, every context flag); VC2HIP_FLAG_CAP_GENERAL sends the third measurement to the general kernel too.
  * Not provided: the capped transcode (vc2hip_transcode_batch_dev keeps one index per picture), more than two indices per
- * picture, a choice of slices by distortion, LD, the command-line tools. */
+ * picture chosen by the library (a caller's map of offsets: vc2hip_set_index_offsets, which this mode fills around), a choice
+ * of slices by distortion, LD, the command-line tools. */
 #define VC2HIP_CAP_Q_TOP 115
 
 enum {
@@ -454,6 +456,39 @@ int vc2hip_set_quant_matrix(vc2hip_ctx *ctx, const int32_t *matrix, int depth);
 /* Copies up to cap entries of the matrix the context holds into out (which may be null when cap is 0) and returns the number
  * held: 3 * depth + 1, or 0 while none is set (VC2HIP_EINVAL for a null context). */
 int vc2hip_get_quant_matrix(const vc2hip_ctx *ctx, int32_t *out, int cap);
+/* Per-slice quantiser index offsets (an extension): a signed offset for every slice of every picture of the encoding batch
+ * calls, so that a caller can say "this part of the picture matters more" -- a region of interest, adaptive quantisation --
+ * under constant quality and under a byte cap alike.
+ *   d_offsets       DEVICE memory, one int8 per slice in raster order; picture i of a batch reads
+ *                   d_offsets[i * picture_stride + s] for slice s, ns = y_slices * x_slices.  NULL: off (picture_stride is
+ *                   not looked at), and every byte and every launch is what it is without this call
+ *   picture_stride  0: one map for every picture of every batch (a static region); otherwise >= ns, which the batch call
+ *                   checks, where ns is known.  Neither the pointer nor the stride has an alignment rule.
+ * With e_s(b) = min(max(b + o_s, 0), 115), every definition of the three HQ VBR modes holds with "slice s at index q" read as
+ * "slice s at e_s(q)":
+ *   HQ_CONSTQ       slice s is coded at e_s(q_index); q_index = 0 with offsets 0 .. 115 is an absolute map.  Errors of the
+ *                   encode surface at vc2hip_sync as for HQ_CONSTQ.
+ *   HQ_CAPPED       picture i gets a base b_i: the smallest b in [q_index, 115] at which the picture coded with the map e_s(b)
+ *                   succeeds and is at most compressed_bytes; 115 if there is none.  A trial raises nothing.  e_s never
+ *                   decreases with b and a slice's bytes never grow with its index up to 115, so the length stays monotone in b.
+ *   HQ_CAPPED_FILL  steps 1 - 5 above with q_i := b_i, len_s(q) := slice s's bytes at e_s(q), eligible := codes at e_s(b_i - 1);
+ *                   a promoted slice gets e_s(b_i - 1), every other e_s(b_i); a slice whose clamp makes the two equal costs 0.
+ * Payload, d_lens, d_qidx (the map e_s), d_recon and d_sse are the slice coder's for that map.  All-zero offsets give, byte for
+ * byte, the call without offsets.  No offset value is invalid.
+ * It is context state, as the layout and the matrix are: the setter launches nothing and waits for nothing and may be called
+ * between any two calls.  The POINTER is held, not the contents: the bytes are read by the kernels of each encoding call on the
+ * context's stream, so the caller orders its writes to the map on that stream as for d_raw, and a captured call keeps the
+ * pointer and sees the contents of each replay.  The lanes of vc2hip_set_streams take the map as one more read-only buffer.
+ * The batch contract holds (nothing allocated beyond the first call of a geometry, no host copy, no wait, graph capture).
+ * Read by vc2hip_encode_batch_dev, vc2hip_encode_recon_batch_dev and vc2hip_encode_fields_batch_dev (the map is indexed by
+ * coded picture, 2 per frame, in slot order).  Ignored by everything else: the host-buffer and _begin / _end calls, the
+ * transcoders, the decoders, the stream calls and the tools.
+ * With offsets set the three calls refuse with VC2HIP_EINVAL, nothing launched and no output byte touched: every mode but
+ * VC2HIP_HQ_CONSTQ, VC2HIP_HQ_CAPPED and VC2HIP_HQ_CAPPED_FILL (HQ_CBR and LD take no offsets); q_index outside
+ * 0 .. VC2HIP_CAP_Q_TOP in any of the three; a non-zero picture_stride below ns.
+ * Not provided: offsets under HQ_CBR / LD, the transcoders, a map chosen by the library (from activity or distortion), the
+ * command-line tools, an effective index above 115. */
+int vc2hip_set_index_offsets(vc2hip_ctx *ctx, const int8_t *d_offsets, size_t picture_stride); /* NULL: off */
 int vc2hip_encode_batch_dev(vc2hip_ctx *ctx, const void *d_raw, int n,
                             const vc2hip_picture_format *fmt, const vc2hip_coding_params *cp,
                             void *d_payload, size_t payload_stride, uint64_t *d_lens);

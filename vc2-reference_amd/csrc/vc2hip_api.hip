@@ -45,6 +45,7 @@ void vc2_launch_plane_emit(Launcher &L, const int32_t *plane, long long plane_st
 void vc2_launch_ll_into_plane(Launcher &L, const int32_t *ll, long long ll_stride, int llh, int llw, int32_t *plane, long long plane_stride,
                               int pw, int depth, int n, hipStream_t s);
 void vc2_launch_fill_i32(Launcher &L, int32_t *p, int32_t v, size_t n, hipStream_t s);
+struct IndexOffsets { const int8_t *p; size_t stride; }; // vc2hip_set_index_offsets, as an encoding call hands it down (p null: none)
 void vc2_launch_fill_u64(Launcher &L, unsigned long long *p, unsigned long long v, size_t n, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
@@ -231,6 +232,10 @@ struct vc2hip_ctx {
   // layout; qm_depth 0: none set, every call uses the default matrix of its wavelet and depth -- effective_matrix)
   int32_t qm[VC2_MAX_BANDS] = {};
   int qm_depth = 0;
+  // vc2hip_set_index_offsets: the caller's device map of one int8 per slice (the POINTER is the state; null: none).  Read by
+  // the three encoding batch entry points, which hand it down; nothing below them looks here.
+  const int8_t *idx_offs = nullptr;
+  size_t idx_offs_stride = 0;
 };
 
 static const char *code_text(int code) {
@@ -2158,7 +2163,7 @@ struct ReconOut {
 };
 static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, int fields, int top_first, int n,
                                const vc2hip_picture_format *fb, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
-                               void *d_payload, size_t payload_stride, uint64_t *d_lens, const ReconOut *ro = nullptr);
+                               void *d_payload, size_t payload_stride, uint64_t *d_lens, const IndexOffsets &io, const ReconOut *ro = nullptr);
 static int run_recon(vc2hip_ctx *c, const Geom &g, const vc2hip_coding_params *cp, int n, const vc2hip_picture_format *f,
                      const PackJob &job, const LdEncParams &lp, const LLPlanes &ll, const struct RawView &in, const ReconOut &ro);
 
@@ -2196,19 +2201,42 @@ static int encode_check(vc2hip_ctx *c, const vc2hip_picture_format *f, const vc2
   const int rc = picture_geom(g, f, cp, false);
   return rc ? set_err(c, rc) : VC2HIP_OK;
 }
+// ---- per-slice index offsets (vc2hip_set_index_offsets) ------------------------------------------
+extern "C" int vc2hip_set_index_offsets(vc2hip_ctx *c, const int8_t *d_offsets, size_t picture_stride) {
+  if (!c) return VC2HIP_EINVAL;
+  c->idx_offs = d_offsets;
+  c->idx_offs_stride = d_offsets ? picture_stride : 0;
+  return VC2HIP_OK;
+}
+// what the three encoding calls refuse under a map, behind encode_check (g: the coded picture's geometry)
+static int offsets_check(vc2hip_ctx *c, const IndexOffsets &io, const vc2hip_coding_params *cp, const Geom &g) {
+  if (!io.p) return VC2HIP_OK;
+  if (cp->mode != VC2HIP_HQ_CONSTQ && cp->mode != VC2HIP_HQ_CAPPED && cp->mode != VC2HIP_HQ_CAPPED_FILL)
+    return set_err(c, VC2HIP_EINVAL, "index offsets are set: only HQ_CONSTQ, HQ_CAPPED and HQ_CAPPED_FILL take them (vc2hip_set_index_offsets(ctx, NULL, 0) clears them)");
+  if (cp->q_index < 0 || cp->q_index > VC2_CAP_Q_TOP) return set_err(c, VC2HIP_EINVAL, "index offsets are set: q_index 0 .. 115");
+  if (io.stride && io.stride < (size_t)g.ys * g.xs)
+    return set_err(c, VC2HIP_EINVAL, "index offsets: picture_stride must be 0 (one map for every picture) or at least y_slices * x_slices");
+  return VC2HIP_OK;
+}
 
-extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
-                                       const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride,
-                                       uint64_t *d_lens) {
+// vc2hip_encode_batch_dev with the map stated: the context's for the entry point, none for the host-buffer and _begin calls
+static int encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
+                            void *d_payload, size_t payload_stride, uint64_t *d_lens, const IndexOffsets &io) {
   if (int rc = batch_args(c, n, f, cp, payload_stride, {{d_raw, 16}, {d_payload, 16}, {d_lens, 8}})) return rc;
   RawLayout lay;
   if (int rc = batch_layout(c, f, lay)) return rc;
   Geom g;
   if (int rc = encode_check(c, f, cp, g)) return rc;
-  const BatchBuf bufs[] = {{d_raw, lay.stride, false}, {d_payload, payload_stride, true}, {d_lens, 8, true}};
+  if (int rc = offsets_check(c, io, cp, g)) return rc;
+  const BatchBuf bufs[] = {{d_raw, lay.stride, false}, {d_payload, payload_stride, true}, {d_lens, 8, true}, {io.p, io.stride, false}};
   return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
-    return encode_batch_common(l, g, at[0], 1, 1, count, f, f, cp, at[1], payload_stride, (uint64_t *)at[2]);
+    return encode_batch_common(l, g, at[0], 1, 1, count, f, f, cp, at[1], payload_stride, (uint64_t *)at[2], {(const int8_t *)at[3], io.stride});
   });
+}
+extern "C" int vc2hip_encode_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
+                                       const vc2hip_coding_params *cp, void *d_payload, size_t payload_stride,
+                                       uint64_t *d_lens) {
+  return encode_batch_dev(c, d_raw, n, f, cp, d_payload, payload_stride, d_lens, c ? IndexOffsets{c->idx_offs, c->idx_offs_stride} : IndexOffsets{nullptr, 0});
 }
 
 extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, int n, const vc2hip_picture_format *f,
@@ -2224,6 +2252,8 @@ extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, i
   if (int rc = batch_layout(c, f, lay)) return rc;
   Geom ge;
   if (int rc = encode_check(c, f, cp, ge)) return rc;
+  const IndexOffsets io = {c->idx_offs, c->idx_offs_stride};
+  if (int rc = offsets_check(c, io, cp, ge)) return rc;
   if (d_recon) {
     const size_t span = (size_t)(n - 1) * lay.stride + lay.extent; // (the file format: n * vc2hip_raw_picture_bytes)
     const uint8_t *raw8 = (const uint8_t *)d_raw, *rec8 = (const uint8_t *)d_recon;
@@ -2238,10 +2268,11 @@ extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, i
         return set_err(c, VC2HIP_EINVAL, "the decoder's padded chroma planes differ from the encoder's: no decoder shows this picture");
   }
   const BatchBuf bufs[] = {{d_raw, lay.stride, false}, {d_payload, payload_stride, true}, {d_lens, 8, true},
-                           {d_recon, lay.stride, true}, {d_sse, 24, true}, {d_qidx, (size_t)ge.ys * ge.xs * 4, true}};
+                           {d_recon, lay.stride, true}, {d_sse, 24, true}, {d_qidx, (size_t)ge.ys * ge.xs * 4, true},
+                           {io.p, io.stride, false}};
   return run_batch(c, n, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
     const ReconOut ro = {at[3], (uint64_t *)at[4], (int32_t *)at[5]};
-    return encode_batch_common(l, ge, at[0], 1, 1, count, f, f, cp, at[1], payload_stride, (uint64_t *)at[2], &ro);
+    return encode_batch_common(l, ge, at[0], 1, 1, count, f, f, cp, at[1], payload_stride, (uint64_t *)at[2], {(const int8_t *)at[6], io.stride}, &ro);
   });
 }
 
@@ -2251,7 +2282,7 @@ extern "C" int vc2hip_encode_recon_batch_dev(vc2hip_ctx *c, const void *d_raw, i
 // The arguments are the entry point's, checked there.
 static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, int fields, int top_first, int n,
                                const vc2hip_picture_format *fb, const vc2hip_picture_format *f, const vc2hip_coding_params *cp,
-                               void *d_payload, size_t payload_stride, uint64_t *d_lens, const ReconOut *ro) {
+                               void *d_payload, size_t payload_stride, uint64_t *d_lens, const IndexOffsets &io, const ReconOut *ro) {
   ENTER(c);
   int rc;
   const int ns = g.ys * g.xs;
@@ -2310,7 +2341,10 @@ static int encode_batch_common(vc2hip_ctx *c, const Geom &g, const void *d_raw, 
     HIPCHK(c, hipMemsetAsync(p.table, 0, (size_t)n * VC2_CAP_ROW * 8, c->stream));
     fill_cbr(p.s, g, st, d_q, b.bytes, cp->scalar, qm, c->cap_general, c->d_err); // (no budgets: the cap is the picture's)
     p.prefix = cp->prefix; p.floor = cp->q_index; p.cap = (unsigned long long)cp->compressed_bytes;
+    p.offs = io.p; p.offs_stride = (long long)io.stride; // (the base b_i is searched, slice s measured and coded at e_s(b_i))
     vc2_launch_cap(c->L, p, n, c->stream);
+  } else if (io.p) {
+    vc2_launch_q_offsets(c->L, d_q, io.p, (long long)io.stride, cp->q_index, ns, n, c->stream);
   } else {
     // quantIndicesConstQ, EncodeStream.cpp:128-138
     vc2_launch_fill_i32(c->L, d_q, cp->q_index, (size_t)n * ns, c->stream);
@@ -3088,9 +3122,12 @@ extern "C" int vc2hip_encode_fields_batch_dev(vc2hip_ctx *c, const void *d_frame
   if (int rc = batch_layout(c, frame_fmt, lay)) return rc;
   Geom g;
   if (int rc = encode_check(c, &ff, cp, g)) return rc;
-  const BatchBuf bufs[] = {{d_frames, lay.stride, false}, {d_payload, 2 * payload_stride, true}, {d_lens, 16, true}};
+  const IndexOffsets io = {c->idx_offs, c->idx_offs_stride}; // by coded picture: a frame is two maps, in slot order
+  if (int rc = offsets_check(c, io, cp, g)) return rc;
+  const BatchBuf bufs[] = {{d_frames, lay.stride, false}, {d_payload, 2 * payload_stride, true}, {d_lens, 16, true}, {io.p, 2 * io.stride, false}};
   return run_batch(c, n_frames, bufs, [&](vc2hip_ctx *l, int count, void *const *at) {
-    return encode_batch_common(l, g, at[0], 2, top_field_first != 0, 2 * count, frame_fmt, &ff, cp, at[1], payload_stride, (uint64_t *)at[2]);
+    return encode_batch_common(l, g, at[0], 2, top_field_first != 0, 2 * count, frame_fmt, &ff, cp, at[1], payload_stride, (uint64_t *)at[2],
+                               {(const int8_t *)at[3], io.stride});
   });
 }
 
@@ -3126,7 +3163,7 @@ extern "C" int vc2hip_encode_picture_hq(vc2hip_ctx *c, const void *raw, const vc
   NEED(c, B_LENS, 64, d_len);
   HIPCHK(c, hipMemcpyAsync(d_raw, raw, rb, hipMemcpyHostToDevice, c->stream));
   const LayoutBypass file_format(c); // (the host-buffer calls keep the file format)
-  int rc = vc2hip_encode_batch_dev(c, d_raw, 1, f, cp, d_pay, pcap, (uint64_t *)d_len);
+  int rc = encode_batch_dev(c, d_raw, 1, f, cp, d_pay, pcap, (uint64_t *)d_len, {nullptr, 0}); // (no index offsets: a device-batch feature)
   if (rc) return rc;
   unsigned long long l = 0;
   HIPCHK(c, hipMemcpyAsync(&l, d_len, 8, hipMemcpyDeviceToHost, c->stream));
@@ -3219,7 +3256,7 @@ extern "C" int vc2hip_encode_picture_begin(vc2hip_ctx *c, const void *raw, const
   if ((rc = need(l, B_RAW, rb + 64, (void **)&d_raw)) || (rc = need(l, B_PAYLOAD, pcap + 64, (void **)&d_pay)) ||
       (rc = need(l, B_LENS, 64, (void **)&d_len))) return fail(rc);
   if (hipMemcpyAsync(d_raw, raw, rb, hipMemcpyHostToDevice, l->stream) != hipSuccess) return fail(VC2HIP_EHIP);
-  if ((rc = vc2hip_encode_batch_dev(l, d_raw, 1, f, cp, d_pay, pcap, (uint64_t *)d_len))) return fail(rc);
+  if ((rc = encode_batch_dev(l, d_raw, 1, f, cp, d_pay, pcap, (uint64_t *)d_len, {nullptr, 0}))) return fail(rc);
   if (hipMemcpyAsync(fl->h_len, d_len, 8, hipMemcpyDeviceToHost, l->stream) != hipSuccess) return fail(VC2HIP_EHIP);
   if (qidx_out && // (from vc2hip_host_alloc like every buffer of a _begin call: a pageable destination makes the call block)
       hipMemcpyAsync(qidx_out, l->buf[B_QIDX].p, (size_t)cp->y_slices * cp->x_slices * 4, hipMemcpyDeviceToHost, l->stream) != hipSuccess)

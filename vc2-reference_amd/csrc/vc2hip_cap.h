@@ -13,8 +13,22 @@
 //            coder would raise at q_i - 1, into CapParams::cost (the FILL instantiations of the two measuring kernels)
 //   fill     k_cap_fill: along the bit-reversed visit order, the slices whose running cost stays within cap - L(q_i) get q_i - 1
 // q_i, the fill flag and the spare bytes travel in words 27 .. 29 of the picture's table row (k_cap_pick).
+//
+// vc2hip_set_index_offsets: with a map of signed offsets o_s, slice s is measured and coded at
+// e_s(b) = min(max(b + o_s, 0), 115) wherever the text above says "index b": the candidates, the bracket and words 27 .. 29
+// are the picture's BASE b_i, and only the index handed to the quantiser and written to qidx is per slice.  e_s never
+// decreases with b and a slice's bytes never grow with its index up to 115, so a picture's length is still monotone in b and
+// the two rounds bracket as before.  The offset forms are instantiations of their own (OFFS = true), as FILL's are: OFFS =
+// false folds every trace of the map away, and the kernels that run without a map keep their code and their registers.
 #pragma once
 #include <type_traits>
+
+__device__ __forceinline__ int cap_eff(int b, int o) { return min(max(b + o, 0), VC2_CAP_Q_TOP); }
+// a slice's offset for a whole wavefront: one byte load, any alignment, made wave-uniform so that the index stays scalar
+template <bool OFFS> __device__ __forceinline__ int cap_slice_offset(const CapParams &p, int pic, int slice) {
+  if constexpr (OFFS) return __builtin_amdgcn_readfirstlane((int)p.offs[(size_t)pic * p.offs_stride + (size_t)slice]);
+  else return 0;
+}
 
 struct CapCand { int q0, step, nc, off; }; // candidate k < nc is index q0 + step * k; its sum is word off + k of the picture's row
 template <bool FILL>
@@ -65,7 +79,7 @@ __device__ __forceinline__ int cap_component_bits(Src src, int n, int n0, int q,
 
 // The general form: one wavefront per slice, any geometry and either store; the slice staged in LDS, or (GLOBAL) read from
 // the store at every candidate.  only_marked: the pass behind k_cap_measure16 over the slices it handed back.
-template <class ST, bool GLOBAL, bool FILL>
+template <class ST, bool GLOBAL, bool FILL, bool OFFS>
 __global__ __launch_bounds__(256) void k_cap_measure(const CapParams p) {
   extern __shared__ __attribute__((aligned(16))) int lds_i[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpw = blockDim.x >> 6;
@@ -92,8 +106,9 @@ __global__ __launch_bounds__(256) void k_cap_measure(const CapParams p) {
       wave_lds_sync(); // no cross-wave sharing of `co`
     }
     unsigned long long val = (unsigned long long)(p.prefix + 4); // a candidate behind the first all-zero one: nothing but the header
+    const int o = cap_slice_offset<OFFS>(p, pic, slice);
     for (int k = 0; k < cd.nc; ++k) {
-      const int tq = cd.q0 + cd.step * k;
+      const int tq = OFFS ? cap_eff(cd.q0 + cd.step * k, o) : cd.q0 + cd.step * k; // (never decreases with k: the early exit below stands)
       bool big = false;
       int need = 0;
       for (int c = 0; c < 3; ++c) {
@@ -133,7 +148,9 @@ __global__ __launch_bounds__(256) void k_cap_measure(const CapParams p) {
 // The quantiser table stops at index 79 as k_cbr_search16's does, and larger adjusted indices read entry 79; here that is
 // exact, so no index is handed back: a magnitude of the 16-bit store is at most 32767, 4 * 32767 < factor(79) = 3 526 975
 // <= factor(a) for 79 <= a <= 115, so both the true quotient and fl(|c| * r79) < 1 are zero.
-template <bool FILL>
+// With index offsets the argument is the same one: every e_s(b) <= 115 by its clamp, a band's index max(e_s(b) - m, 0) no
+// larger, and entry() keeps the table offset inside 0 .. 79 * 16 whatever the offset's value.
+template <bool FILL, bool OFFS>
 __global__ __launch_bounds__(256, VC2_CBR16_WPE) void k_cap_measure16(const CapParams p) {
   __shared__ uint4 s_tab[80]; // by quantiser index: (rounded-up 4 / factor as a float, -, -, -)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -224,9 +241,10 @@ __global__ __launch_bounds__(256, VC2_CBR16_WPE) void k_cap_measure16(const CapP
       return need;
     };
     unsigned long long val = (unsigned long long)(p.prefix + 4);
+    const int o = cap_slice_offset<OFFS>(p, pic, slice);
     for (int k = 0; k < cd.nc; ++k) {
       bool bad = false; // (a length byte beyond 255; a code beyond 32 bits needs a quotient above 65534: not from 16-bit magnitudes)
-      const int need = need_bytes(cd.q0 + cd.step * k, bad);
+      const int need = need_bytes(OFFS ? cap_eff(cd.q0 + cd.step * k, o) : cd.q0 + cd.step * k, bad);
       if (lane == k) val = bad ? VC2_CAP_NOFIT : (unsigned long long)(p.prefix + 4 + need);
       if (!bad && need == 0) break;
     }
@@ -242,6 +260,8 @@ __global__ __launch_bounds__(256, VC2_CBR16_WPE) void k_cap_measure16(const CapP
 // smallest fitting index of the bracket, written to the picture's n_slices entries of qidx -- and, for HQ_CAPPED_FILL, q_i,
 // whether the picture is to be filled (it left the floor and fits at q_i) and its spare bytes cap - L(q_i), L(q_i) from
 // the table: the round-2 entry that fitted, or the round-1 entry of an index floor + 8 k.
+// OFFS: q is the picture's base b_i, slice i's entry of qidx is e_i(b_i), and words 27 .. 29 carry b_i.
+template <bool OFFS>
 __global__ __launch_bounds__(256) void k_cap_pick(const CapParams p) {
   const int pic = blockIdx.y;
   unsigned long long *row = p.table + (size_t)pic * VC2_CAP_ROW;
@@ -263,7 +283,7 @@ __global__ __launch_bounds__(256) void k_cap_pick(const CapParams p) {
   int hit = -1;
   for (int j = count - 1; j >= 0; --j) if (fits(row[VC2_CAP_R2 + j])) { q = base + 1 + j; hit = j; }
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < p.s.n_slices) p.s.qidx[(size_t)pic * p.s.n_slices + i] = q;
+  if (i < p.s.n_slices) p.s.qidx[(size_t)pic * p.s.n_slices + i] = OFFS ? cap_eff(q, (int)p.offs[(size_t)pic * p.offs_stride + (size_t)i]) : q;
   if (i == 0) { // (words no thread of this launch reads)
     const unsigned long long len = hit >= 0 ? row[VC2_CAP_R2 + hit] : ((q - p.floor) % 8 == 0 ? row[(q - p.floor) / 8] : VC2_CAP_NOFIT);
     const bool fill = q > p.floor && fits(len);
@@ -275,6 +295,8 @@ __global__ __launch_bounds__(256) void k_cap_pick(const CapParams p) {
 // slice rev_B(k) (positions past the picture are skipped), and the slice there gets q_i - 1 iff it has a cost and the running
 // sum of the costs through k, in 64 bits, is at most the spare bytes.  256 positions per turn: an inclusive scan in each
 // wavefront, the four totals through LDS, the carry in a register.  Pictures with nothing to fill keep k_cap_pick's indices.
+// OFFS: qi is the base b_i; a promoted slice gets e_s(b_i - 1), every other e_s(b_i) (equal where the clamp acts: its cost was 0).
+template <bool OFFS>
 __global__ __launch_bounds__(256) void k_cap_fill(const CapParams p) {
   __shared__ unsigned long long s_tot[4];
   const int pic = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -307,7 +329,10 @@ __global__ __launch_bounds__(256) void k_cap_fill(const CapParams p) {
       if (w < wave) before += t;
       total += t;
     }
-    if (valid) q[slice] = eligible && before + v <= spare ? qi - 1 : qi;
+    if (valid) {
+      const int b = eligible && before + v <= spare ? qi - 1 : qi;
+      q[slice] = OFFS ? cap_eff(b, (int)p.offs[(size_t)pic * p.offs_stride + (size_t)slice]) : b;
+    }
     carry += total;
     __syncthreads(); // s_tot is written again
   }
@@ -328,6 +353,7 @@ void vc2_launch_cap(Launcher &L, const CapParams &p0, int n_pictures, hipStream_
   const bool global = per_wave > 160 * 1024; // the slice does not fit in LDS: every candidate reads it from the store
   const int wpw = global ? 4 : std::max(1, std::min(4, (int)((160 * 1024) / per_wave)));
   static const char *const names[3] = {"cap_measure1", "cap_measure2", "cap_measure3"};
+  const bool offs = p.offs != nullptr; // the offset forms: the same rounds under the same names
   for (int round = 0; round < (p.cost ? 3 : 2); ++round) {
     const bool fill = round == 2;
     vc2_prof_begin(L, names[round], s);
@@ -335,8 +361,10 @@ void vc2_launch_cap(Launcher &L, const CapParams &p0, int n_pictures, hipStream_
     p.s.only_marked = 0;
     if (fast) {
       const int per_wg = 4 * CBR_SPW;
-      if (fill) VC2_LAUNCH(L, k_cap_measure16<true>, dim3((g.n_slices + per_wg - 1) / per_wg, n_pictures), dim3(256), 0, s, p16);
-      else VC2_LAUNCH(L, k_cap_measure16<false>, dim3((g.n_slices + per_wg - 1) / per_wg, n_pictures), dim3(256), 0, s, p16);
+      const dim3 grid16((g.n_slices + per_wg - 1) / per_wg, n_pictures);
+      void (*const fast16)(const CapParams) = fill ? (offs ? k_cap_measure16<true, true> : k_cap_measure16<true, false>)
+                                                   : (offs ? k_cap_measure16<false, true> : k_cap_measure16<false, false>);
+      VC2_LAUNCH(L, fast16, grid16, dim3(256), 0, s, p16);
       p.s.only_marked = 1;
     }
     const int gx = p.s.only_marked ? std::min((g.n_slices + wpw - 1) / wpw, 64) : (g.n_slices + wpw - 1) / wpw;
@@ -344,8 +372,9 @@ void vc2_launch_cap(Launcher &L, const CapParams &p0, int n_pictures, hipStream_
     auto general = [&](auto st, auto gl, auto fl) { // one launch of k_cap_measure<ST, GLOBAL, FILL>
       using ST = decltype(st);
       constexpr bool GL = decltype(gl)::value, FL = decltype(fl)::value;
-      if (!GL) vc2_allow_lds((const void *)k_cap_measure<ST, GL, FL>, 160 * 1024);
-      VC2_LAUNCH(L, (k_cap_measure<ST, GL, FL>), grid, block, GL ? 0 : wpw * per_wave, s, p);
+      void (*const kernel)(const CapParams) = offs ? k_cap_measure<ST, GL, FL, true> : k_cap_measure<ST, GL, FL, false>;
+      if (!GL) vc2_allow_lds((const void *)kernel, 160 * 1024);
+      VC2_LAUNCH(L, kernel, grid, block, GL ? 0 : wpw * per_wave, s, p);
     };
     auto by_store = [&](auto gl, auto fl) {
       if (g.store16) general(int16_t(), gl, fl);
@@ -355,8 +384,8 @@ void vc2_launch_cap(Launcher &L, const CapParams &p0, int n_pictures, hipStream_
     else { if (fill) by_store(std::false_type(), std::true_type()); else by_store(std::false_type(), std::false_type()); }
     vc2_prof_end(L, s);
     vc2_prof_begin(L, fill ? "cap_fill" : "cap_pick", s);
-    if (fill) VC2_LAUNCH(L, k_cap_fill, dim3(1, n_pictures), dim3(256), 0, s, p);
-    else VC2_LAUNCH(L, k_cap_pick, dim3(round ? (g.n_slices + 255) / 256 : 1, n_pictures), dim3(256), 0, s, p);
+    if (fill) VC2_LAUNCH(L, offs ? k_cap_fill<true> : k_cap_fill<false>, dim3(1, n_pictures), dim3(256), 0, s, p);
+    else VC2_LAUNCH(L, offs ? k_cap_pick<true> : k_cap_pick<false>, dim3(round ? (g.n_slices + 255) / 256 : 1, n_pictures), dim3(256), 0, s, p);
     vc2_prof_end(L, s);
   }
 }

@@ -357,6 +357,8 @@ struct CapParams {
   int prefix, floor;
   int round;                  // 0 / 1; 2: HQ_CAPPED_FILL's per-slice round
   unsigned *cost;             // HQ_CAPPED_FILL (null otherwise): n_pictures * n_slices, len_s(q_i - 1) - len_s(q_i) or VC2_CAP_NOCOST
+  const int8_t *offs;         // vc2hip_set_index_offsets (null: none, the kernels without a map run): slice s of picture i reads
+  long long offs_stride;      // offs[i * offs_stride + s]; 0: one map for every picture.  Any alignment
 };
 
 // ------------------------------------------------------------------------------------------
@@ -395,6 +397,9 @@ void vc2_launch_compact(Launcher &L, const uint8_t *slots, int slot_bytes, const
                         int n_slices, int n_pictures, hipStream_t s);
 void vc2_launch_cbr(Launcher &L, const CbrParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_cap(Launcher &L, const CapParams &p, int n_pictures, hipStream_t s);
+// HQ_CONSTQ under vc2hip_set_index_offsets: qidx[i, s] = min(max(base + offs[i * offs_stride + s], 0), VC2_CAP_Q_TOP)
+void vc2_launch_q_offsets(Launcher &L, int32_t *qidx, const int8_t *offs, long long offs_stride, int base, int n_slices,
+                          int n_pictures, hipStream_t s);
 void vc2_launch_unpack(Launcher &L, const UnpackParams &p, int n_pictures, hipStream_t s);
 void vc2_launch_cbr_index(Launcher &L, const uint8_t *payload, long long stride, const unsigned long long *lens, const int32_t *budget,
                           const uint32_t *cbr_offs, unsigned long long total, uint32_t *offsets, int n_slices, int prefix, int scalar,

@@ -4218,6 +4218,19 @@ void vc2_launch_fill_i32(Launcher &L, int32_t *p, int32_t v, size_t n, hipStream
   VC2_LAUNCH(L, k_fill_i32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, v, n);
   vc2_prof_end(L, s);
 }
+// The index map of an HQ_CONSTQ call under vc2hip_set_index_offsets, in place of k_fill_i32: one
+// thread per slice, blockIdx.y the picture.  A byte load per thread (the map has no alignment, and stride 0 sends every
+// picture to the same bytes), a dword store; the last workgroup of a picture is cut by the bound.
+__global__ __launch_bounds__(256) void k_q_offsets(int32_t *qidx, const int8_t *offs, long long offs_stride, int base, int n_slices) {
+  const int s = blockIdx.x * 256 + threadIdx.x, pic = blockIdx.y;
+  if (s < n_slices) qidx[(size_t)pic * n_slices + s] = cap_eff(base, (int)offs[(size_t)pic * offs_stride + (size_t)s]);
+}
+void vc2_launch_q_offsets(Launcher &L, int32_t *qidx, const int8_t *offs, long long offs_stride, int base, int n_slices,
+                          int n_pictures, hipStream_t s) {
+  vc2_prof_begin(L, "q_offsets", s);
+  VC2_LAUNCH(L, k_q_offsets, dim3((unsigned)((n_slices + 255) / 256), n_pictures), dim3(256), 0, s, qidx, offs, offs_stride, base, n_slices);
+  vc2_prof_end(L, s);
+}
 void vc2_launch_fill_u64(Launcher &L, unsigned long long *p, unsigned long long v, size_t n, hipStream_t s) {
   vc2_prof_begin(L, "fill", s);
   VC2_LAUNCH(L, k_fill_u64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, v, n);

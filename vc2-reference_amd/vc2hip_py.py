@@ -99,6 +99,7 @@ EXPORTS = [
     "vc2hip_set_packed_format", "vc2hip_packed_picture_bytes",
     "vc2hip_transcode_batch_dev", "vc2hip_transcode_cbr_batch_dev",
     "vc2hip_set_quant_matrix", "vc2hip_get_quant_matrix", "vc2hip_picture_header_qm", "vc2hip_parse_picture_header",
+    "vc2hip_set_index_offsets",
 ]
 
 
@@ -182,6 +183,8 @@ def load_library():
                                                 C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
     lib.vc2hip_set_quant_matrix.argtypes = [vp, vp, C.c_int]
     lib.vc2hip_get_quant_matrix.argtypes = [vp, i32p, C.c_int]
+    if hasattr(lib, "vc2hip_set_index_offsets"):   # (an older build named by VC2HIP_LIB has none: the A/B tools time it all the same)
+        lib.vc2hip_set_index_offsets.argtypes = [vp, vp, C.c_size_t]
     lib.vc2hip_stream_write_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams), C.POINTER(StreamParams),
                                             vp, C.c_size_t, vp]
     lib.vc2hip_stream_write_fragments_dev.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(CodingParams),
@@ -686,6 +689,12 @@ class Vc2Hip:
         entries of 0 ... 255 in the order of quant_matrix(kernel, depth); None: the default of each call's wavelet and depth"""
         _keep, ptr, depth = _matrix_arg(matrix)
         self._chk(self.lib.vc2hip_set_quant_matrix(self.h, ptr, depth))
+
+    def set_index_offsets(self, d_offsets=None, picture_stride=0):
+        """a signed int8 offset per slice for the three encoding batch calls from now on: d_offsets is a DEVICE address (an
+        int, e.g. tensor.data_ptr()) of one byte per slice in raster order, picture i reading from i * picture_stride
+        (0: one map for every picture); None: off.  The pointer is held, the bytes are read by each call's kernels"""
+        self._chk(self.lib.vc2hip_set_index_offsets(self.h, d_offsets, picture_stride if d_offsets is not None else 0))
 
     def set_streams(self, k):
         self._chk(self.lib.vc2hip_set_streams(self.h, k))

@@ -2581,6 +2581,8 @@ void vc2_launch_unpack(Launcher &L, const UnpackParams &p0, int n_pictures, hipS
 //               -> (exit offset into the next chunk, slices started)       [parallel in e, chunk]
 //   2. chain  : per picture, follow entry -> exit through the chunk tables  [one lane/picture]
 //   3. emit   : per chunk, walk again from the now-known entry and write the offsets
+// On the 8 and 16 KiB plans only the first chunk of every group of 16 gets such a table; the other fifteen are walked from
+// the few offsets at which chains leave it (k_index_follow).
 // ------------------------------------------------------------------------------------------
 // chunk size: 16 KiB, or 32 KiB when a slice can be longer than 8191 bytes (entry offsets must stay below the
 // chunk size and chunk-relative positions below 2^16)
@@ -2637,11 +2639,11 @@ template <int CH, int GS>
 __global__ __launch_bounds__(idx_threads(CH, GS)) void k_index_tables_nx(const uint8_t *payload, long long stride,
                                                                  const unsigned long long *lens, unsigned *tables,
                                                                  int n_chunks, int E, int prefix, int scalar, unsigned *err, const unsigned *skip,
-                                                                 int merge) {
+                                                                 int merge, int chunk_step) {
   constexpr int NT = idx_threads(CH, GS), NP = CH >> GS; // candidate positions of a chunk
   if (skip && *skip == 0) return; // the HQ_CBR short cut found every slice where the byte budgets put it (k_cbr_index_check)
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_b[];
-  const int chunk = blockIdx.x, pic = blockIdx.y;
+  const int chunk = blockIdx.x * chunk_step, pic = blockIdx.y; // (chunk_step: every chunk, or the anchors alone -- k_index_follow)
   // a length beyond the picture's slot (hostile or uninitialised) is an error and is never followed out of the slot
   if (chunk == 0 && threadIdx.x == 0 && lens[pic] > (unsigned long long)stride) atomicOr(err, VC2_DEVERR_STREAM);
   const unsigned long long plen = min(lens[pic], (unsigned long long)stride), c0 = (unsigned long long)chunk * CH;
@@ -2801,6 +2803,151 @@ __global__ __launch_bounds__(256) void k_index_group(const unsigned long long *l
     const uint2 t = idx_entry<WORD>(tables, t0 + e);
     const uint2 r = res[t.x >> gsh];
     groups[((size_t)pic * n_groups + g) * E + e] = make_uint2(r.x, t.y + r.y);
+  }
+}
+
+// Follower walk: the group function without the tables of the group's chunks 1 .. 15.  Only the group's first chunk (its
+// anchor) gets a table for every entry offset (k_index_tables_nx with chunk_step = IDX_GROUP).  The E entries leave the
+// anchor at a few distinct offsets, and chains that meet stay together: on a coded UHD picture 7 distinct chains are left
+// behind the first 16 KiB chunk, 3 behind the second, 1 from the third on.  So the other fifteen chunks are walked from
+// those survivors alone -- one lane each, three dependent LDS reads per slice -- instead of from every entry offset:
+//   - the followers' bytes lie end to end behind the anchor; they are staged `step` bytes (CH or a part of it) at a time, as
+//     stage_chunk does (clamped to the payload, zero behind it), the next two steps' pieces held in registers during the walk
+//   - at every chunk boundary a survivor's word (exit << 16 | slices) goes to the slot of its entry offset in that chunk's
+//     table row -- the only words of the row k_index_chain will ever read, since the chain enters the chunk at a survivor --
+//     and the exits are deduplicated again
+//   - every distinct exit of the anchor keeps where its chain stands and the slices it has passed; the group function of
+//     every entry offset is the anchor's word and that
+// There is no cap on survivors: a stream whose chains never meet keeps up to EU of them, the lists are sized for EU and the
+// walks run in passes of the workgroup's threads (a survivor's state between steps is kept in W[]).
+// The chunk function is k_index_tables_nx's exactly: an entry at or behind `lim` starts no slice, and a slice that ends behind
+// the payload end leaves the chunk at offset 0 unless it really reaches the next chunk.
+constexpr int IDX_FOLLOW_NT = 256;
+// 16-byte pieces per thread and step: 3 (steps of up to 12 KiB with their E + 16 bytes) or 7 (16384 + 8191 + 16 bytes at most)
+constexpr int IDX_FOLLOW_PIECES_SMALL = 3, IDX_FOLLOW_PIECES = 7;
+static size_t idx_follow_stage(int step, int E) { return (size_t)((step + E + 16 + 15) & ~15); }
+static size_t idx_follow_lds(int step, int E, int EU) { return idx_follow_stage(step, E) + (size_t)EU * 14 + ((size_t)(EU + 31) / 32) * 4; }
+
+template <int PIECES>
+__device__ __forceinline__ void idx_follow_fetch(uint4 (&piece)[PIECES], const uint8_t *pay, unsigned long long plen,
+                                                 unsigned long long base, int nbytes) {
+#pragma unroll
+  for (int p = 0; p < PIECES; ++p) {
+    const int i = (p * IDX_FOLLOW_NT + (int)threadIdx.x) * 16;
+    if (i >= nbytes) continue;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    const unsigned long long a = base + i;
+    if (a + 16 <= plen) v = *(const uint4 *)(pay + a);
+    else {
+      unsigned w[4] = {0, 0, 0, 0};
+      for (int k = 0; k < 16; ++k) if (a + k < plen) w[k >> 2] |= (unsigned)pay[a + k] << (8 * (k & 3));
+      v = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    piece[p] = v;
+  }
+}
+
+template <int PIECES>
+__global__ __launch_bounds__(IDX_FOLLOW_NT) void k_index_follow(const uint8_t *payload, long long stride, const unsigned long long *lens,
+                                                                unsigned *tables, uint2 *groups, int n_chunks, int n_groups, int E,
+                                                                int prefix, int scalar, int CH, int step, const unsigned *skip, int gsh) {
+  constexpr int NT = IDX_FOLLOW_NT;
+  if (skip && *skip == 0) return; // the HQ_CBR short cut found every slice where the byte budgets put it (k_cbr_index_check)
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_f[];
+  const int g = blockIdx.x, pic = blockIdx.y, c0 = g * IDX_GROUP;
+  const unsigned long long plen = min(lens[pic], (unsigned long long)stride);
+  if ((unsigned long long)c0 * CH >= plen) return;
+  const int EU = E >> gsh, nbytes = (step + E + 16 + 15) & ~15, nsub = CH / step, nbits = (EU + 31) / 32;
+  unsigned *W = (unsigned *)(lds_f + nbytes);                   // per entry offset: a survivor's walk (position << 16 | slices; at the chunk's end its table word)
+  unsigned *cnt = W + EU;                                       // per distinct exit of the anchor: slices its chain has passed since
+  unsigned *need = cnt + EU;                                    // one bit per offset: some chain enters the next chunk here
+  unsigned short *cur = (unsigned short *)(need + nbits);       // per distinct exit of the anchor: where its chain stands
+  unsigned short *first = cur + EU;                             // the distinct exits of the anchor, dense
+  unsigned short *list = first + EU;                            // the survivors: the distinct entry offsets of the chunk in hand, dense
+  __shared__ unsigned s_n[2];                                   // survivors of the chunk in hand / of the next one, in turns
+  int nfol = 0;                                                 // chunks behind the anchor that hold payload
+  for (int k = 1; k < IDX_GROUP; ++k) {
+    const int c = c0 + k;
+    if (c >= n_chunks || (unsigned long long)c * CH >= plen) break;
+    ++nfol;
+  }
+  const uint8_t *pay = payload + (size_t)pic * stride;
+  const unsigned long long f0 = (unsigned long long)(c0 + 1) * CH;
+  const int T = nfol * nsub;
+  uint4 piece_a[PIECES], piece_b[PIECES]; // the bytes of the next two steps, on their way while this one is walked
+  if (T > 0) idx_follow_fetch(piece_a, pay, plen, f0, nbytes);
+  if (T > 1) idx_follow_fetch(piece_b, pay, plen, f0 + step, nbytes);
+  const unsigned *tab0 = tables + ((size_t)pic * n_chunks + c0) * EU;
+  for (int t = threadIdx.x; t < nbits; t += NT) need[t] = 0;
+  if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
+  __syncthreads();
+  for (int e = threadIdx.x; e < EU; e += NT) {
+    const unsigned x = (tab0[e] >> 16) >> gsh;
+    if (!(atomicOr(&need[x >> 5], 1u << (x & 31)) >> (x & 31) & 1u)) {
+      const unsigned i = atomicAdd(&s_n[0], 1u);
+      first[i] = list[i] = (unsigned short)x;
+      cur[x] = (unsigned short)x;
+      cnt[x] = 0;
+    }
+  }
+  __syncthreads();
+  const int n1 = (int)s_n[0];
+  int n = n1;
+  auto turn = [&](uint4 (&piece)[PIECES], int t) { // step t of the group: its bytes into LDS, the survivors through them
+    const int k = 1 + t / nsub, j = t % nsub, c = c0 + k;
+#pragma unroll
+    for (int p = 0; p < PIECES; ++p) {
+      const int i = (p * NT + (int)threadIdx.x) * 16;
+      if (i < nbytes) *(uint4 *)(lds_f + i) = piece[p];
+    }
+    __syncthreads();
+    if (t + 2 < T) idx_follow_fetch(piece, pay, plen, f0 + (unsigned long long)(t + 2) * step, nbytes);
+    const int lim = (int)min((unsigned long long)CH, plen - (unsigned long long)c * CH); // never walk the zero fill behind the payload
+    const int lo = j * step, hi = lo + step;
+    const bool last = j == nsub - 1;
+    unsigned *tab = tables + ((size_t)pic * n_chunks + c) * EU;
+    for (int i = threadIdx.x; i < n; i += NT) {
+      const int x = list[i];
+      int pos, hops;
+      if (j == 0) {
+        pos = x << gsh; hops = 0;
+        if (pos >= lim) pos = CH; // starts behind the payload end: no slice
+      } else {
+        const unsigned w = W[x];
+        pos = (int)(w >> 16); hops = (int)(w & 0xFFFFu);
+      }
+      while (pos < hi) {
+        const int q = pos + slice_len_lds(lds_f, pos - lo, prefix, scalar);
+        pos = q >= lim ? max(q, CH) : q;
+        ++hops;
+      }
+      const unsigned w = (unsigned)(last ? pos - CH : pos) << 16 | (unsigned)hops;
+      W[x] = w;
+      if (last) tab[x] = w;
+    }
+    if (last) for (int b = threadIdx.x; b < nbits; b += NT) need[b] = 0;
+    __syncthreads();
+    if (!last) return;
+    for (int m = threadIdx.x; m < n1; m += NT) {
+      const int x0 = first[m];
+      const unsigned w = W[cur[x0]];
+      const unsigned x = (w >> 16) >> gsh;
+      cur[x0] = (unsigned short)x;
+      cnt[x0] += w & 0xFFFFu;
+      if (!(atomicOr(&need[x >> 5], 1u << (x & 31)) >> (x & 31) & 1u)) list[atomicAdd(&s_n[k & 1], 1u)] = (unsigned short)x;
+    }
+    if (threadIdx.x == 0) s_n[(k + 1) & 1] = 0;
+    __syncthreads();
+    n = (int)s_n[k & 1];
+  };
+  for (int t = 0; t < T; t += 2) {
+    turn(piece_a, t);
+    if (t + 1 < T) turn(piece_b, t + 1);
+  }
+  for (int e = threadIdx.x; e < EU; e += NT) {
+    const unsigned t = tab0[e];
+    const unsigned x0 = (t >> 16) >> gsh;
+    groups[((size_t)pic * n_groups + g) * EU + e] = make_uint2((unsigned)cur[x0] << gsh, (t & 0xFFFFu) + cnt[x0]);
   }
 }
 
@@ -3001,6 +3148,18 @@ void vc2_launch_slice_index(Launcher &L, const uint8_t *payload, long long paylo
   unsigned *tables = (unsigned *)workspace;
   uint2 *entries = (uint2 *)(((size_t)(tables + (size_t)n_pictures * n_chunks * EU) + 15) & ~(size_t)15);
   const size_t stage_bytes = (size_t)((ch + E + 16 + 15) & ~15);
+  const int n_groups = (n_chunks + IDX_GROUP - 1) / IDX_GROUP; // <= 1024 (g_entry)
+  // (exit offsets are below E and fit 16 bits up to IDX_MAX_E; the dedupe tables need 14 bytes of LDS per entry)
+  static const bool no_dedupe = vc2_tune_int("VC2HIP_IDX_NO_DEDUPE", 0) != 0;
+  const int dedupe = !no_dedupe && EU <= 8192;
+  // Anchors and followers (k_index_follow) wherever a step's bytes fit the follower's pieces and its lists 64 KiB of LDS:
+  // the 8 and 16 KiB chunks.  32 KiB chunks (E from 8192 on) and VC2HIP_IDX_NO_DEDUPE keep a table per chunk and compose them.
+  // (the follower's staging step: 8 KiB, or with VC2HIP_IDX_FOLLOW_STEP another power-of-two part of the chunk.  Measured on
+  // 128 UHD scalar-2 pictures, 16 KiB chunks, one step of prefetch: steps of 16 / 8 / 4 / 2 KiB 0.46 / 0.40 / 0.45 / 0.53 ms)
+  static const int follow_step = vc2_tune_int("VC2HIP_IDX_FOLLOW_STEP", 0);
+  const int fstep = follow_step >= 1024 && follow_step <= ch && (follow_step & (follow_step - 1)) == 0 ? follow_step : std::min(ch, 8192);
+  const bool follow = dedupe && idx_follow_stage(fstep, E) <= (size_t)IDX_FOLLOW_PIECES * IDX_FOLLOW_NT * 16 &&
+                      idx_follow_lds(fstep, E, EU) <= (size_t)64 * 1024;
   vc2_prof_begin(L, "slice_index_tables", s);
   {
     // merged walks (see the kernel): entry regions of up to 4096 offsets whose landing region lies inside the chunk
@@ -3010,8 +3169,8 @@ void vc2_launch_slice_index(Launcher &L, const uint8_t *payload, long long paylo
 #define VC2_IDX_TABLES(CH, GS)                                                                                                    \
   do {                                                                                                                        \
     vc2_allow_lds((const void *)k_index_tables_nx<CH, GS>, lds);                                                                  \
-    VC2_LAUNCH(L, (k_index_tables_nx<CH, GS>), dim3(n_chunks, n_pictures), dim3(idx_threads(CH, GS)), lds, s, payload, payload_stride, \
-               lens, tables, n_chunks, E, prefix, scalar, err, skip, merge);                                                  \
+    VC2_LAUNCH(L, (k_index_tables_nx<CH, GS>), dim3(follow ? n_groups : n_chunks, n_pictures), dim3(idx_threads(CH, GS)), lds, s, payload, payload_stride, \
+               lens, tables, n_chunks, E, prefix, scalar, err, skip, merge, follow ? IDX_GROUP : 1);                          \
   } while (0)
 #define VC2_IDX_TABLES_G(CH) do { if (gsh == 0) VC2_IDX_TABLES(CH, 0); else if (gsh == 1) VC2_IDX_TABLES(CH, 1); else VC2_IDX_TABLES(CH, 2); } while (0)
     if (ch == 8192) VC2_IDX_TABLES_G(8192);
@@ -3021,19 +3180,27 @@ void vc2_launch_slice_index(Launcher &L, const uint8_t *payload, long long paylo
 #undef VC2_IDX_TABLES
   }
   vc2_prof_end(L, s);
-  const int n_groups = (n_chunks + IDX_GROUP - 1) / IDX_GROUP; // <= 1024 (g_entry)
   // (the third level costs a launch: 5 us; it pays from a few hundred groups on -- UHD-2 pictures: 0.163 -> 0.132 ms)
   const int n_supers = n_groups > 128 ? (n_groups + IDX_GROUP - 1) / IDX_GROUP : 0;
   uint2 *groups = entries + (size_t)n_pictures * n_chunks;
   uint2 *supers = groups + (size_t)n_pictures * n_groups * EU;
   vc2_prof_begin(L, "slice_index_chain", s);
   {
-    // (exit offsets are below E and fit 16 bits up to IDX_MAX_E; the dedupe tables need 14 bytes of LDS per entry)
-    static const bool no_dedupe = vc2_tune_int("VC2HIP_IDX_NO_DEDUPE", 0) != 0;
-    const int dedupe = !no_dedupe && EU <= 8192;
     const size_t glds = dedupe ? ((size_t)((EU + 1) & ~1) * 4 + (size_t)EU * 8 + (size_t)EU * 2 + 16) : 0;
     if (glds) { vc2_allow_lds((const void *)k_index_group<true>, glds); vc2_allow_lds((const void *)k_index_group<false>, glds); }
-    VC2_LAUNCH(L, k_index_group<true>, dim3(n_groups, n_pictures), dim3(256), glds, s, lens, payload_stride, (const void *)tables, groups, n_chunks, n_groups, EU, (long long)ch, skip, dedupe, gsh);
+    if (follow) {
+      const size_t flds = idx_follow_lds(fstep, E, EU);
+#define VC2_IDX_FOLLOW(PIECES)                                                                                                  \
+  do {                                                                                                                          \
+    vc2_allow_lds((const void *)k_index_follow<PIECES>, flds);                                                                  \
+    VC2_LAUNCH(L, k_index_follow<PIECES>, dim3(n_groups, n_pictures), dim3(IDX_FOLLOW_NT), flds, s, payload, payload_stride, lens, \
+               tables, groups, n_chunks, n_groups, E, prefix, scalar, ch, fstep, skip, gsh);                                    \
+  } while (0)
+      if (idx_follow_stage(fstep, E) <= (size_t)IDX_FOLLOW_PIECES_SMALL * IDX_FOLLOW_NT * 16) VC2_IDX_FOLLOW(IDX_FOLLOW_PIECES_SMALL);
+      else VC2_IDX_FOLLOW(IDX_FOLLOW_PIECES);
+#undef VC2_IDX_FOLLOW
+    } else
+      VC2_LAUNCH(L, k_index_group<true>, dim3(n_groups, n_pictures), dim3(256), glds, s, lens, payload_stride, (const void *)tables, groups, n_chunks, n_groups, EU, (long long)ch, skip, dedupe, gsh);
     if (n_supers) VC2_LAUNCH(L, k_index_group<false>, dim3(n_supers, n_pictures), dim3(256), glds, s, lens, payload_stride, (const void *)groups, supers, n_groups, n_supers, EU, (long long)ch * IDX_GROUP, skip, dedupe, gsh);
   }
   // (one lane follows the super-groups of a picture; then a thread per super-group / group expands it: sixteen dependent reads each, all at once)
